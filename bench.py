@@ -11,6 +11,12 @@ task in allocate, nodes visited until the first fit in backfill: SURVEY.md §8d)
 
 One JSON line on rank 0; see DESIGN.md §7 for the roofline accounting (M: 2.125 B per evaluation written by the
 matrix kernel + inputs once) and the cpu_baseline definition.
+
+A plain run sets up, warms up, times the --steps cycles and prints the line: its figures are the ones the timed cycles
+produce themselves (value, ms_per_step, the engine's per-kernel times, the per-round matrix launch's roofline).  --full
+adds what takes runs or reads of its own: the session load timed seven times, the materialised T x N matrix launches
+(`roofline`, `roofline_eval*`) with the committed PMC summaries, the CPU baselines with the oracle's check of the bind
+set, and the default configuration's variants.  --dump-outputs DIR writes what the last timed cycle computed.
 """
 import argparse
 import importlib
@@ -27,6 +33,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs: the .npy files of one run stay below 64 MB in all
+DUMP_SAMPLE_SEED = 20260601   # ... a larger output keeps the same seeded sample of rows from run to run
 RANK_SEED_STRIDE = 7919   # --gpus N: rank k schedules the snapshot of seed + RANK_SEED_STRIDE * k (tests/golden/make_bench_rank_digests.py)
 
 BINPACK_CONF = """
@@ -65,6 +73,23 @@ def _k(n):
     return f"{n // 1000}k" if n >= 1000 and n % 1000 == 0 else str(n)
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (the engine's ids and kinds are uint32: exact in a double).  When they
+    would take more than `limit` bytes, every array keeps the same share of its rows, chosen by a fixed seed and kept in order, and
+    <name>_rows.npy says which rows those are."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= limit else limit / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), int(len(a) * frac), replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,6 +109,10 @@ def main():
                     "giving the core up between polls after a short spin (N = 1 only)")
     ap.add_argument("--preempt", action="store_true", help="BASELINE configs[4] names allocate + backfill + preempt: a step becomes reset -> allocate -> backfill -> "
                     "preempt under the default tiers plus conformance (scripts/time_preempt.py's configuration); with --gpus N every replica runs the evict action and the journals are compared (kube-batch_amd/dist.py)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: session load times, the materialised matrix launches' "
+                    "rooflines and the committed PMC summaries, the CPU baselines with the oracle's check of the bind set, the default configuration's variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed cycles: what the last one computed as DIR/<name>.npy in float64 — decisions (task, node, kind "
+                    "in order), the bind set, with --preempt the Statement journal and the evictions (rank 0)")
     args = ap.parse_args()
 
     import numpy as np
@@ -274,18 +303,18 @@ def main():
         eng = engine.Engine(conf, device=local_rank, window=args.window, commit_batch=args.commit_batch, flags=kbm.abi.FLAG_SPIN_WAIT if args.spin_wait else 0)
         eng.load(snap)
         # what the Go shim pays every cycle (host pre-processing + H2D into a live engine, warm buffers): kb_session_load returns behind its
-        # own synchronisation, so the call is the cost.  Seven loads: the median is reported, the maximum beside it.
-        load_samples = []
-        for _ in range(7):
-            tl0 = time.perf_counter()
-            eng.load(snap)
-            load_samples.append((time.perf_counter() - tl0) * 1e3)
-        load_ms = sorted(load_samples)[len(load_samples) // 2]
+        # own synchronisation, so the call is the cost.  Seven loads (--full): the median is reported, the maximum beside it.
+        load_samples, load_ms = [], None
+        if args.full:
+            for _ in range(7):
+                tl0 = time.perf_counter()
+                eng.load(snap)
+                load_samples.append((time.perf_counter() - tl0) * 1e3)
+            load_ms = sorted(load_samples)[len(load_samples) // 2]
 
         def step():
             eng.reset()
-            for a in actions:
-                getattr(eng, "run_" + a)()
+            return [getattr(eng, "run_" + a)() for a in actions]     # each action's decisions (--dump-outputs keeps the last cycle's)
 
     if world > 1 or force_sharded:
         load_ms, load_samples = None, []
@@ -302,8 +331,9 @@ def main():
     coll0 = dict(runner.collective_times(), replicated=runner.replicated_rounds, checks=runner.deferred_checks) if dist_mode == "sharded" else None
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     t1 = time.perf_counter()
     s1 = eng.stats()
@@ -316,6 +346,13 @@ def main():
 
     binds = eng.binds()
     n_binds = int((binds != kbm.abi.KB_NONE).sum())
+    if args.dump_outputs and rank == 0 and last is not None:
+        # before anything else runs on the engine: the last timed cycle's decisions (N = 1: one array per action), its bind set and evict results
+        dec = np.concatenate(last) if isinstance(last, list) else last
+        outputs = {"decisions": dec.reshape(-1, 3), "binds": binds}
+        if args.preempt:
+            outputs.update(journal=eng.journal().reshape(-1, 4), evictions=eng.evictions())
+        dump_outputs(args.dump_outputs, outputs)
     d = {k: s1[k] - s0[k] for k in s1}
     evals = d["evals"]
     replicas_agree = None
@@ -408,7 +445,7 @@ def main():
     roofline_cycle = roof(d["matrix_evals"] / N / launches, d["matrix_ms"] / launches, launches,
                           "per-round launch inside the timed region (distinct shapes of one window)")
     full_reps = 5
-    full_ms = eng.bench_matrix(0, T, reps=full_reps) if world == 1 else 0.0
+    full_ms = eng.bench_matrix(0, T, reps=full_reps) if world == 1 and args.full else 0.0    # plain run: `roofline` is the per-round launch's
     if args.diverse:     # shapes > rows / 16: the engine evaluates every row directly instead of expanding shape rows (kb_engine.cpp)
         full_label, full_kernel = f"kb_bench_matrix rows [0,{T}) x {N} nodes: direct per-row evaluation, runs of adjacent equal rows evaluated once", "k_matrix_runs"
     else:
@@ -427,11 +464,11 @@ def main():
         roofline_eval_all = roof(T, ms_a, 2, f"kb_bench_matrix rows [0,{T}) x {N} nodes: {T} x {N} evaluations, nothing shared", "k_matrix<4,32>")
     # HBM bytes per launch from the PMC passes of scripts/gpu_r5.sh profile (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate
     # runs; KB units; FETCH_SIZE doubled per MI355X_MICROARCH.md's gfx950 correction).  Cannot be collected inside this
-    # process, so the committed summary of the same command is read back; null when it is absent or for another config.
+    # process, so the committed summary of the same command is read back; null when it is absent or for another config (or without --full).
     import glob
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     from kernel_sources_sha import kernel_sources_sha, kernel_tu_sha, read_tu_stamp
-    live_sha = kernel_sources_sha(ROOT)
+    live_sha = kernel_sources_sha(ROOT) if args.full else None
 
     def stale(csv_path, tu):
         """None when the committed summary was measured on kernels compiled from THESE sources, else the reason it may not be quoted.  The stamps
@@ -449,7 +486,7 @@ def main():
             return f"{os.path.relpath(csv_path, ROOT)} carries no kernel_sources.sha256: it cannot be tied to the kernels of this tree"
         rec = open(stamp).read().split()[0]
         return None if rec == live_sha else f"{os.path.relpath(csv_path, ROOT)} was measured on other device sources (sha256 {rec[:12]}, this tree {live_sha[:12]})"
-    found = sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "rocprofv3_pmc_k_matrix.csv")),
+    found = sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "rocprofv3_pmc_k_matrix.csv")) if args.full else [],
                    key=lambda f: int("".join(c for c in os.path.basename(os.path.dirname(f)) if c.isdigit()) or 0))
     pmc = found[-1] if found else ""                # the newest round's summary
     if full_ms > 0 and pmc and not args.diverse:     # the diverse-shape stress evaluates every row directly: another kernel mix
@@ -488,7 +525,7 @@ def main():
                        "rounds_per_step": d["rounds"] / args.steps, "us_per_round": round(commit_ms_step * 1e3 / max(1.0, d["rounds"] / args.steps), 1),
                        "streaming_equivalent_frac_of_hbm_peak": round(value * b_node / 1e9 / HBM_PEAK_GBS, 4),   # SURVEY 8d accounting (S), see streaming_equivalent
                        "counters": None}
-    found_c = sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "rocprofv3_pmc_k_commit.csv")),
+    found_c = sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", "rocprofv3_pmc_k_commit.csv")) if args.full else [],
                      key=lambda f: int("".join(c for c in os.path.basename(os.path.dirname(f)) if c.isdigit()) or 0))
     if found_c and stale(found_c[-1], "kb_commit_sel.hip"):
         roofline_commit["counters_refused"] = stale(found_c[-1], "kb_commit_sel.hip")
@@ -517,7 +554,7 @@ def main():
         "metric": f"pod-node scoring evals/sec + binds/sec, {_k(snap.n_tasks)} tasks x {_k(snap.n_nodes)} nodes snapshot",
         "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "strong" if dist_mode == "sharded" else "weak",   # the task-row split divides ONE session (total work fixed); sessions mode: one session per GPU
-        "vs_baseline": None, "dtype": "f64+i64", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f64+i64", "data": "synthetic", "full": bool(args.full),
         "config": {"workload": f"BASELINE configs[{args.config - 1}]: {snap.n_tasks} tasks x {snap.n_nodes} nodes, "
                                f"{snap.n_jobs} gang jobs, {snap.n_queues} queues, R={R}, {'+'.join(actions)}, "
                                f"plugins priority,gang,drf,predicates,proportion,nodeorder ({weights})",
@@ -561,7 +598,7 @@ def main():
 
     if args.config == 5 and not args.cpu_sample_tasks:
         args.cpu_sample_tasks = 2000           # 1M x 50k: the faithful loop needs minutes; a bounded sample, as section 4 of the task allows
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # the CPU baseline is reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # the CPU baseline is reported at N=1 only
         import oracle
         oracle.build()
         threads = min(16, os.cpu_count() or 1)    # util/scheduler_helper.go:84: 16 workers
@@ -601,7 +638,7 @@ def main():
                                                "sample": f"the whole allocate action ({o.evals} reference-equivalent evals, {c1 - c0:.1f} s) by the oracle's "
                                                          "incremental mode (per-shape cached rows + one-node repairs + max-tree) on one thread"}
             o.close()
-    default_run = (rank == 0 and world == 1 and args.config == 3 and not (args.diverse or args.survey_nodes or args.preempt) and not args.no_cpu_baseline
+    default_run = (args.full and rank == 0 and world == 1 and args.config == 3 and not (args.diverse or args.survey_nodes or args.preempt) and not args.no_cpu_baseline
                    and (args.scale == 1.0 or os.environ.get("KB_BENCH_VARIANTS") == "1") and os.environ.get("KB_BENCH_VARIANTS") != "0")
     if default_run:
         # the unfriendly inputs, in the driver's own record: SURVEY 8d's literal node sizes (no capacity pressure: dirty nodes win most rows)

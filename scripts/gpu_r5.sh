@@ -24,7 +24,7 @@ ms() { python -c "import json,sys; d=json.loads(open('$1').read().strip().splitl
 bench_ab() {   # name, env assignments..., -- bench args
   local name="$1"; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  timeout 400 env "${envs[@]}" KB_K5_STATS=1 python bench.py --no-cpu-baseline "$@" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"
+  timeout 400 env "${envs[@]}" KB_K5_STATS=1 python bench.py --full --no-cpu-baseline "$@" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"
   echo "bench $name rc=$? $(ms "$out/bench_${name}.json")" | tee -a "$out/summary.txt"
   grep -h "kb select\|kb host\|kb probe" "$out/bench_${name}.err" | tee -a "$out/summary.txt"
 }
@@ -33,16 +33,16 @@ first)
   timeout 900 python -m pytest tests/test_gpu_reload.py -q -m gpu -p no:cacheprovider -x -s > "$out/pytest_reload.txt" 2>&1; echo "reload module rc=$? $(tail -1 "$out/pytest_reload.txt")" | tee -a "$out/summary.txt"
   grep -h "^soak" "$out/pytest_reload.txt" | tee -a "$out/summary.txt"
   timeout 1200 python -m pytest tests -q -m gpu -p no:cacheprovider --deselect tests/test_gpu_reload.py > "$out/pytest_gpu.txt" 2>&1; echo "gpu suite (without the reload module) rc=$? $(tail -1 "$out/pytest_gpu.txt")" | tee -a "$out/summary.txt"
-  timeout 600 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 600 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   python -c "import json; d=json.loads(open('$out/bench_default.json').read().strip().splitlines()[-1]); print(json.dumps(d.get('variants'), indent=1)); print('loads', d.get('session_load_ms_samples'))" | tee -a "$out/summary.txt"
   for cfg in 3 4 5; do
-    KB_LOAD_TRACE=1 timeout 300 python bench.py --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$out/load_c${cfg}.json" 2> "$out/session_load_trace_config${cfg}.txt"
+    KB_LOAD_TRACE=1 timeout 300 python bench.py --full --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$out/load_c${cfg}.json" 2> "$out/session_load_trace_config${cfg}.txt"
     echo "config $cfg load: $(ms "$out/load_c${cfg}.json")" | tee -a "$out/summary.txt"
   done
   ;;
 loads)
   for cfg in 3 4 5; do
-    KB_LOAD_TRACE=1 timeout 300 python bench.py --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$out/load_c${cfg}.json" 2> "$out/session_load_trace_config${cfg}.txt"
+    KB_LOAD_TRACE=1 timeout 300 python bench.py --full --config $cfg --steps 1 --warmup 0 --no-cpu-baseline > "$out/load_c${cfg}.json" 2> "$out/session_load_trace_config${cfg}.txt"
     echo "config $cfg load: $(ms "$out/load_c${cfg}.json")" | tee -a "$out/summary.txt"
   done
   ;;
@@ -115,14 +115,14 @@ fuse)   # the repair workgroups inside the selection kernel's launch (default) a
   ;;
 trace)
   for cfg in "3" "4"; do
-    KB_ENGINE_LIB=$PWD/kube-batch_amd/libkbengine_trace.so KB_K5_STATS=1 python bench.py --no-cpu-baseline --config ${cfg} --steps 2 --warmup 1 \
+    KB_ENGINE_LIB=$PWD/kube-batch_amd/libkbengine_trace.so KB_K5_STATS=1 python bench.py --full --no-cpu-baseline --config ${cfg} --steps 2 --warmup 1 \
       > "$out/trace_c${cfg}.json" 2> "$out/trace_c${cfg}.err"
     echo "== trace c${cfg} $(ms "$out/trace_c${cfg}.json")" | tee -a "$out/summary.txt"; grep -h "kb K5 trace\|kb K5\] rounds [0-9]\|kb select" "$out/trace_c${cfg}.err" | tee -a "$out/summary.txt"
   done
   ;;
 profile)   # rocprofv3 evidence of the default bench command: kernel stats, HBM bytes of the matrix launches, SQ counters of the commit kernel
   export TMPDIR=/tmp
-  CMD="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+  CMD="python $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
   P="$PWD/$out"
   ( cd /tmp
     rocprofv3 --kernel-trace --stats -f csv -d "$P/trace" -o bench -- $CMD > "$P/bench_trace.log" 2>&1
@@ -138,7 +138,7 @@ profile)   # rocprofv3 evidence of the default bench command: kernel stats, HBM 
 pmc_matrix)   # the matrix launches' HBM bytes and the kernel stats again, after a change to kb_kernels.hip that left the commit kernels' translation
               # unit alone (scripts/kernel_sources_sha.py --tu): FETCH_SIZE, WRITE_SIZE, then the kernel trace — in that order, the call may be cut
   export TMPDIR=/tmp
-  CMD="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+  CMD="python $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
   P="$PWD/$out"
   ( cd /tmp
     rocprofv3 --pmc FETCH_SIZE -f csv --kernel-include-regex "k_matrix|k_expand" -d "$P/pmc_fetch" -o bench -- $CMD > "$P/bench_pmc_fetch.log" 2>&1
@@ -151,7 +151,7 @@ suite)
   timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider "$@" > "$out/pytest_gpu.txt" 2>&1; echo "gpu suite rc=$? $(tail -1 "$out/pytest_gpu.txt")" | tee -a "$out/summary.txt"
   ;;
 bench)
-  timeout 600 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 600 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   bench_ab survey_nodes -- --config 3 --survey-nodes --steps 5 --warmup 2 --verify
   bench_ab config4 -- --config 4 --steps 5 --warmup 2 --verify
   bench_ab config2 -- --config 2 --steps 10 --warmup 3 --verify
@@ -167,7 +167,7 @@ final)   # the round's closing evidence on the final tree: whole suite, rocprofv
   bash scripts/gpu_r5.sh profile > "$out/profile_step.txt" 2>&1
   python scripts/summarize_profile.py r5_profile profiles/round5 >> "$out/profile_step.txt" 2>&1
   python scripts/trace_gaps.py gpurun_out/r5_profile/trace/bench_kernel_trace.csv 3 > "$out/gaps_config3.txt" 2>&1; head -12 "$out/gaps_config3.txt" | tee -a "$out/summary.txt"
-  timeout 600 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 600 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   python -c "import json; d=json.loads(open('$out/bench_default.json').read().strip().splitlines()[-1]); print(json.dumps({k: (v['ms_per_step'], v['verified']) for k, v in d['variants'].items()})); print('roofline', d['roofline']['frac'], d['roofline']['traffic'], d['roofline'].get('traffic_refused')); print('loads', d['session_load_ms_samples'])" | tee -a "$out/summary.txt"
   bench_ab survey_nodes -- --config 3 --survey-nodes --steps 5 --warmup 2 --verify
   bench_ab config4 -- --config 4 --steps 5 --warmup 2 --verify

@@ -19,7 +19,7 @@ ms() { python -c "import json,sys; d=json.loads(open('$1').read().strip().splitl
 bench_ab() {   # name, env assignments..., -- bench args
   local name="$1"; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  timeout 400 env "${envs[@]}" KB_K5_STATS=1 python bench.py --no-cpu-baseline "$@" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"
+  timeout 400 env "${envs[@]}" KB_K5_STATS=1 python bench.py --full --no-cpu-baseline "$@" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"
   echo "bench $name rc=$? $(ms "$out/bench_${name}.json")" | tee -a "$out/summary.txt"
   grep -h "kb select\|kb host\|kb probe\|kb K5" "$out/bench_${name}.err" | tee -a "$out/summary.txt"
 }
@@ -34,7 +34,7 @@ ab_cfgs() {
 }
 trace_cfgs() {
   for cfg in "$@"; do
-    KB_ENGINE_LIB=$PWD/kube-batch_amd/libkbengine_trace.so KB_K5_STATS=1 timeout 300 python bench.py --no-cpu-baseline --config ${cfg} --steps 2 --warmup 1 \
+    KB_ENGINE_LIB=$PWD/kube-batch_amd/libkbengine_trace.so KB_K5_STATS=1 timeout 300 python bench.py --full --no-cpu-baseline --config ${cfg} --steps 2 --warmup 1 \
       > "$out/trace_c${cfg}.json" 2> "$out/trace_c${cfg}.err"
     echo "== trace c${cfg} $(ms "$out/trace_c${cfg}.json")" | tee -a "$out/summary.txt"; grep -h "kb K5 trace\|kb K5\] rounds [0-9]\|kb select" "$out/trace_c${cfg}.err" | tee -a "$out/summary.txt"
   done
@@ -61,7 +61,7 @@ gaps)   # where a cycle's time goes outside the commit kernels:   gaps [configs.
   if [ $# -eq 0 ]; then set -- 5; fi
   export TMPDIR=/tmp
   for cfg in "$@"; do
-    ( cd /tmp; KB_K5_STATS=1 rocprofv3 --kernel-trace -f csv -d "$OLDPWD/$out/trace_c${cfg}" -o bench -- python "$OLDPWD/bench.py" --config ${cfg} --steps 2 --warmup 1 --no-cpu-baseline \
+    ( cd /tmp; KB_K5_STATS=1 rocprofv3 --kernel-trace -f csv -d "$OLDPWD/$out/trace_c${cfg}" -o bench -- python "$OLDPWD/bench.py" --full --config ${cfg} --steps 2 --warmup 1 --no-cpu-baseline \
         > "$OLDPWD/$out/gaps_c${cfg}.json" 2> "$OLDPWD/$out/gaps_c${cfg}.err" )
     echo "== gaps c${cfg} $(ms "$out/gaps_c${cfg}.json")" | tee -a "$out/summary.txt"
     grep -h "kb host\|kb probe\|kb overlap" "$out/gaps_c${cfg}.err" | tee -a "$out/summary.txt"
@@ -74,7 +74,7 @@ mix)   # one call: the differential modules under both commit kernels, the defau
   timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_adversarial.py tests/test_gpu_regressions.py tests/test_gpu_fuzz.py tests/test_gpu_fullsize.py tests/test_gpu_interpod.py tests/test_gpu_waterfill.py \
     -q -m gpu -p no:cacheprovider --maxfail=10 > "$out/pytest_subset.txt" 2>&1; echo "differential modules, both commit kernels rc=$? $(tail -1 "$out/pytest_subset.txt")" | tee -a "$out/summary.txt"
   grep -h "^FAILED\|^ERROR" "$out/pytest_subset.txt" | head -20 | tee -a "$out/summary.txt"
-  timeout 900 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   python - "$out/bench_default.json" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -84,7 +84,7 @@ for k, v in d.get("variants", {}).items():
 PY
   for cfg in 3 4; do
     for t in 1 0; do
-      KB_EXPAND_TILES=$t timeout 300 python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > "$out/expand_c${cfg}_tiles${t}.json" 2> "$out/expand_c${cfg}_tiles${t}.err"
+      KB_EXPAND_TILES=$t timeout 300 python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > "$out/expand_c${cfg}_tiles${t}.json" 2> "$out/expand_c${cfg}_tiles${t}.err"
       python -c "import json; d=json.loads(open('$out/expand_c${cfg}_tiles${t}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('expand config $cfg tiles=$t', r['kernel'], 'frac', r['frac'], 'ms', r['avg_launch_ms'], 'eval-only', d['roofline_eval']['frac'], d['roofline_eval_all_rows']['frac'])" | tee -a "$out/summary.txt"
     done
   done
@@ -97,7 +97,7 @@ profile)   # rocprofv3 evidence of the default bench command on THIS tree: kerne
            # SQ counters of the commit kernel with the commit workgroup ALONE in its launch (KB_PROFILE_SOLO_COMMIT=1 KB_FUSE_REPAIR=0: attributable to
            # its eight waves; the default launch carries ~30 mostly idle workgroups) — then   python scripts/summarize_profile.py r6_profile profiles/round6
   export TMPDIR=/tmp
-  CMD="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+  CMD="python $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
   P="$PWD/$out"
   ( cd /tmp
     rocprofv3 --kernel-trace --stats -f csv -d "$P/trace" -o bench -- $CMD > "$P/bench_trace.log" 2>&1
@@ -117,11 +117,11 @@ profile)   # rocprofv3 evidence of the default bench command on THIS tree: kerne
 mix2)  # the tiled expansion again (rows preloaded), the evict action's host timeline at 1M x 50k, the profile passes, two gloo ranks on the one GPU
   for cfg in 3 4; do
     for t in 1 0; do
-      KB_EXPAND_TILES=$t timeout 300 python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > "$out/expand_c${cfg}_tiles${t}.json" 2> "$out/expand_c${cfg}_tiles${t}.err"
+      KB_EXPAND_TILES=$t timeout 300 python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline > "$out/expand_c${cfg}_tiles${t}.json" 2> "$out/expand_c${cfg}_tiles${t}.err"
       python -c "import json; d=json.loads(open('$out/expand_c${cfg}_tiles${t}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('expand config $cfg tiles=$t', r['kernel'], 'frac', r['frac'], 'ms', r['avg_launch_ms'], 'eval-only', d['roofline_eval']['frac'], d['roofline_eval_all_rows']['frac'])" | tee -a "$out/summary.txt"
     done
   done
-  KB_EVICT_TRACE=1 timeout 600 python bench.py --config 5 --preempt --steps 2 --warmup 1 --no-cpu-baseline --verify > "$out/bench_c5_preempt.json" 2> "$out/bench_c5_preempt.err"
+  KB_EVICT_TRACE=1 timeout 600 python bench.py --full --config 5 --preempt --steps 2 --warmup 1 --no-cpu-baseline --verify > "$out/bench_c5_preempt.json" 2> "$out/bench_c5_preempt.err"
   echo "config 5 + preempt rc=$? $(ms "$out/bench_c5_preempt.json")" | tee -a "$out/summary.txt"; grep -h "kb evict" "$out/bench_c5_preempt.err" | tail -2 | tee -a "$out/summary.txt"
   bash scripts/gpu_r6.sh profile > "$out/profile_step.txt" 2>&1; tail -16 "$out/profile_step.txt" | tee -a "$out/summary.txt"
   KB_SCALE_GLOO=1 timeout 900 bash scripts/scale_curve.sh "$out/scale" 3 > "$out/scale_curve_log.txt" 2>&1; cat "$out/scale/scale_curve.txt" | tee -a "$out/summary.txt"
@@ -130,7 +130,7 @@ expand)  # the tiled expansion: bench's own event timing (normal run) for the de
          # (KB_EXPAND_TILES=0), each twice; then the same under rocprofv3 --kernel-trace (the profiler's durations beside the bench's own)
   one() { # name, env..., -- args
     local name="$1"; shift; local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-    timeout 300 env "${envs[@]}" python bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/x_${name}.json" 2> "$out/x_${name}.err"
+    timeout 300 env "${envs[@]}" python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/x_${name}.json" 2> "$out/x_${name}.err"
     python -c "import json; d=json.loads(open('$out/x_${name}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$name', r['kernel'], 'frac', r['frac'], 'ms', r['avg_launch_ms'])" | tee -a "$out/summary.txt"
   }
   base="KB_ENGINE_LIB=$PWD/kube-batch_amd/libkbengine_base.so"   # (here: an earlier build of the tiled kernel, if one is beside the default)
@@ -147,7 +147,7 @@ expand)  # the tiled expansion: bench's own event timing (normal run) for the de
   P="$PWD/$out"
   for v in tiles; do
     envs=()
-    ( cd /tmp; env "${envs[@]}" rocprofv3 --kernel-trace --stats -f csv -d "$P/trace_$v" -o bench -- python /root/repo/bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$P/trace_$v.log" 2>&1 ) || true
+    ( cd /tmp; env "${envs[@]}" rocprofv3 --kernel-trace --stats -f csv -d "$P/trace_$v" -o bench -- python "$OLDPWD/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$P/trace_$v.log" 2>&1 ) || true
     grep -h "k_expand\|k_matrix<1, 16>" "$P/trace_$v/bench_kernel_stats.csv" 2>/dev/null | cut -c1-140 | tee -a "$out/summary.txt"
     grep -h '"metric"' "$P/trace_$v.log" | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('under rocprofv3 ($v):', d['roofline']['avg_launch_ms'], d['roofline']['frac'])" | tee -a "$out/summary.txt"
   done
@@ -158,7 +158,7 @@ final)   # the closing evidence on the tree as it stands: the whole -m gpu suite
   grep -h "^FAILED\|^ERROR" "$out/pytest_gpu.txt" | head -20 | tee -a "$out/summary.txt"
   R6_TAG= bash scripts/gpu_r6.sh profile > "$out/profile_step.txt" 2>&1; tail -14 "$out/profile_step.txt" | tee -a "$out/summary.txt"
   mkdir -p "$out/profiles_round6" && cp -r profiles/round6/. "$out/profiles_round6/"
-  timeout 900 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   python - "$out/bench_default.json" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -190,7 +190,7 @@ variants)  # same-box A/B of builds of the selection kernel: kube-batch_amd/libk
   ;;
 xchunk)  # rows per chunk of the tiled expansion: the default build (64) against libkbengine_x8.so / _x16.so and the row copy, configs 3 and 4, three times each
   one() { local name="$1"; shift; local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-    timeout 300 env "${envs[@]}" python bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/x_${name}.json" 2> "$out/x_${name}.err"
+    timeout 300 env "${envs[@]}" python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$out/x_${name}.json" 2> "$out/x_${name}.err"
     python -c "import json; d=json.loads(open('$out/x_${name}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$name', 'frac', r['frac'], 'ms', r['avg_launch_ms'])" | tee -a "$out/summary.txt"; }
   for rep in 1 2 3; do
     for cfg in 3 4; do
@@ -205,7 +205,7 @@ xchunk)  # rows per chunk of the tiled expansion: the default build (64) against
 profile_bench)  # the profile passes (summarised on the box into profiles/round6), then the default bench line, which quotes them
   R6_TAG= bash scripts/gpu_r6.sh profile > "$out/profile_step.txt" 2>&1; tail -14 "$out/profile_step.txt" | tee -a "$out/summary.txt"
   mkdir -p "$out/profiles_round6" && cp -r profiles/round6/. "$out/profiles_round6/"
-  timeout 900 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
+  timeout 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench default rc=$? $(ms "$out/bench_default.json")" | tee -a "$out/summary.txt"
   python - "$out/bench_default.json" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -219,7 +219,7 @@ PY
 pmc_matrix)  # the matrix launches' HBM bytes and the kernel stats again after a change that left the commit kernels' translation unit alone (host side of the
              # expansion, kb_kernels.hip): FETCH_SIZE, WRITE_SIZE, kernel trace; summarised on the box (the commit kernel's lines of profiles/round6 stay)
   export TMPDIR=/tmp
-  CMD="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+  CMD="python $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
   P="$PWD/gpurun_out/r6_profile"; mkdir -p "$P"
   python scripts/kernel_sources_sha.py > "$P/kernel_sources.sha256"; python scripts/kernel_sources_sha.py --tu > "$P/kernel_tu.sha256"
   ( cd /tmp
@@ -230,7 +230,7 @@ pmc_matrix)  # the matrix launches' HBM bytes and the kernel stats again after a
   python scripts/summarize_profile.py r6_profile profiles/round6 2>&1 | tail -2 | tee -a "$out/summary.txt"
   mkdir -p "$out/profiles_round6" && cp -r profiles/round6/rocprofv3_* profiles/round6/kernel_* profiles/round6/bench_under_rocprofv3_kernel_trace.json "$out/profiles_round6/"
   cat profiles/round6/rocprofv3_pmc_k_matrix.csv | cut -c1-150 | tee -a "$out/summary.txt"
-  timeout 600 python bench.py --no-cpu-baseline --verify > "$out/bench_c3.json" 2> "$out/bench_c3.err"
+  timeout 600 python bench.py --full --no-cpu-baseline --verify > "$out/bench_c3.json" 2> "$out/bench_c3.err"
   python -c "import json; d=json.loads(open('$out/bench_c3.json').read().strip().splitlines()[-1]); r=d['roofline']; print('bench: ms', d['ms_per_step'], 'verified', d.get('verified_bind_set_equals_oracle'), 'roofline', r['frac'], r['avg_launch_ms'], 'traffic', r.get('traffic'), r.get('traffic_refused'), 'ratio', (r.get('traffic') or 0) / r['bytes_per_launch'])" | tee -a "$out/summary.txt"
   ;;
 subset)

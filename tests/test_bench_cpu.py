@@ -1,7 +1,8 @@
 """bench.py's own control flow — argument handling, the timed loop, the roofline / cpu_baseline / verification objects, the one JSON line the
 driver parses — run on the CPU: the engine library is the emulated build of tests/test_emu_engine_cpu.py and torch.cuda is answered by a
 stand-in.  The NUMBERS of such a run mean nothing (an emulated device has no bandwidth); what is checked is that the line has every
-field of the bench contract, that the bind set is verified against the oracle in the same run, and that a flag cannot break the default."""
+field of the bench contract, that a --full line verifies the bind set against the oracle in the same run, that a plain line times exactly
+the cycles it is asked for and nothing else, what --dump-outputs writes, and that a flag cannot break the default."""
 import importlib
 import io
 import json
@@ -43,7 +44,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_default_line_has_every_field_and_verifies_itself(monkeypatch):
-    out = _run_bench(monkeypatch, ["--scale", "0.02", "--steps", "2", "--warmup", "1"])
+    out = _run_bench(monkeypatch, ["--scale", "0.02", "--steps", "2", "--warmup", "1", "--full"])
     for k in CONTRACT:
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "evals/s" and out["vs_baseline"] is None
@@ -62,10 +63,10 @@ def test_default_line_has_every_field_and_verifies_itself(monkeypatch):
 
 
 def test_default_run_carries_the_unfriendly_inputs(monkeypatch):
-    """the driver's default line also times and verifies SURVEY 8d's literal node sizes and BASELINE configs[3] (variants), reports the
+    """the --full line also times and verifies SURVEY 8d's literal node sizes and BASELINE configs[3] (variants), reports the
     oracle's incremental mode beside the 16-thread loop, and the matrix kernel's own evaluation rates (scaled here; full size on the GPU box)"""
     monkeypatch.setenv("KB_BENCH_VARIANTS", "1")
-    out = _run_bench(monkeypatch, ["--scale", "0.02", "--steps", "1", "--warmup", "0"])
+    out = _run_bench(monkeypatch, ["--scale", "0.02", "--steps", "1", "--warmup", "0", "--full"])
     assert set(out["variants"]) == {"survey_nodes", "config4_binpack", "config2"}      # (+ diverse, config5, config5_preempt at full size: their digests are the full size's)
     for v in out["variants"].values():
         assert v["verified"] is True and v["ms_per_step"] > 0 and v["binds"] > 0 and v["evals_per_s"] > 0
@@ -75,16 +76,89 @@ def test_default_run_carries_the_unfriendly_inputs(monkeypatch):
         assert out[k]["bound"] == "hbm" and out[k]["kernel"].startswith("k_matrix") and out[k]["frac"] >= 0
 
 
-@pytest.mark.parametrize("argv", [["--config", "4", "--scale", "0.02", "--steps", "1", "--warmup", "0"],
+@pytest.mark.parametrize("argv", [["--config", "4", "--scale", "0.02", "--steps", "1", "--warmup", "0", "--full"],
                                   ["--config", "3", "--scale", "0.02", "--diverse", "--steps", "1", "--no-cpu-baseline", "--verify"],
                                   ["--config", "5", "--scale", "0.004", "--steps", "1", "--preempt", "--no-cpu-baseline", "--verify"],
-                                  ["--config", "3", "--scale", "0.02", "--steps", "2", "--preempt"]])
+                                  ["--config", "3", "--scale", "0.02", "--steps", "2", "--preempt", "--full"]])
 def test_variants_produce_a_verified_line(monkeypatch, argv):
     out = _run_bench(monkeypatch, argv)
     assert out["verified_bind_set_equals_oracle"] is True and out["verified_evals_equal_oracle"] is True, out
     if "--preempt" in argv:
         assert out["verified_evictions_equal_oracle"] is True and out["verified_journal_equals_oracle"] is True and out["journal_entries"] >= 0
         assert "allocate+backfill+preempt" in out["config"]["workload"]
+
+
+def test_plain_run_times_the_steps_it_is_asked_for_and_nothing_else(monkeypatch):
+    """Without --full the line is the headline alone: --warmup cycles, then exactly --steps timed cycles, on a session loaded once; no
+    materialised-matrix launch, no oracle (no CPU baseline, no variants).  The contract's fields mean what they do in a --full line."""
+    calls = {"reset": 0, "load": 0, "bench_matrix": 0}
+    for name in calls:
+        def counted(self, *a, _orig=getattr(engine.Engine, name), _name=name, **k):
+            calls[_name] += 1
+            return _orig(self, *a, **k)
+        monkeypatch.setattr(engine.Engine, name, counted)
+    oracle = importlib.import_module("oracle")
+    monkeypatch.setattr(oracle, "Oracle", lambda *a, **k: pytest.fail("a plain run opened the oracle"))
+    out = _run_bench(monkeypatch, ["--scale", "0.02", "--steps", "3", "--warmup", "2"])
+    assert calls == {"reset": 5, "load": 1, "bench_matrix": 0}, calls
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["full"] is False
+    assert out["metric"].startswith("pod-node scoring evals/sec") and out["unit"] == "evals/s" and out["higher_is_better"] is True and out["dtype"] == "f64+i64"
+    assert out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] - out["evals_per_step"] / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    assert "cpu_baseline" not in out and "variants" not in out and out["session_load_ms"] is None
+    assert out["roofline"] == out["roofline_cycle"] and out["roofline_eval"] is None and out["roofline_commit"]["counters"] is None
+
+
+@pytest.mark.parametrize("preempt", [False, True])
+def test_dump_outputs_are_the_last_timed_cycle(monkeypatch, tmp_path, preempt):
+    """--dump-outputs DIR: the last timed cycle's decisions, bind set (and with --preempt the journal and the evictions) as float64 .npy files,
+    the same from run to run with the same arguments, and what the oracle computes on the same snapshot"""
+    import numpy as np
+    argv = ["--scale", "0.02", "--steps", "2", "--warmup", "1"] + (["--preempt"] if preempt else [])
+    for d in ("a", "b"):
+        _run_bench(monkeypatch, argv + ["--dump-outputs", str(tmp_path / d)])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["decisions.npy", "binds.npy"] + (["evictions.npy", "journal.npy"] if preempt else []))
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float64 and np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert sum(a.nbytes for a in got.values()) < 64e6
+    kbm = importlib.import_module("kube-batch_amd")
+    bench = importlib.import_module("bench")
+    conf = kbm.conf.load_scheduler_conf(bench.PREEMPT_CONF) if preempt else kbm.conf.load_scheduler_conf()
+    oracle = importlib.import_module("oracle")
+    oracle.build()
+    o = oracle.Oracle(conf, kbm.snapshot.synth(kbm.snapshot.synth_config(3, 0.02)))
+    o.run(["allocate", "backfill"] + (["preempt"] if preempt else []))
+    assert len(got["decisions"]) > 0 and np.array_equal(got["binds"], o.binds())
+    if preempt:
+        assert np.array_equal(got["journal"], o.journal()) and np.array_equal(got["evictions"], o.evictions())
+    else:
+        assert np.array_equal(got["decisions"], o.decisions())
+    o.close()
+
+
+def test_dump_outputs_keep_a_fixed_sample_under_the_size_limit(tmp_path):
+    """an output larger than the limit is written as the same seeded sample of every array's rows, in order, with the rows' indices beside it"""
+    import numpy as np
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(1)
+    arrays = {"decisions": rng.integers(0, 2**32 - 1, (5000, 3), dtype=np.uint32), "binds": rng.integers(0, 2**32 - 1, 20000, dtype=np.uint32)}
+    limit = 100_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["binds.npy", "binds_rows.npy", "decisions.npy", "decisions_rows.npy"]
+    loaded = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert sum(a.nbytes for a in loaded.values()) <= limit
+    share = limit / sum(8 * a.size + 8 * len(a) for a in arrays.values())      # a row in float64 with its index
+    for name, a in arrays.items():
+        rows, vals = loaded[name + "_rows.npy"], loaded[name + ".npy"]
+        assert rows.dtype == np.float64 and vals.dtype == np.float64 and np.all(np.diff(rows) > 0)
+        assert len(rows) == int(len(a) * share)                           # every array keeps the same share of its rows
+        assert np.array_equal(vals, a[rows.astype(np.int64)].astype(np.float64))
+    for n in names:
+        assert np.array_equal(loaded[n], np.load(tmp_path / "b" / n)), n
 
 
 def test_smoke_entry_point_runs_end_to_end(monkeypatch, capsys):
