@@ -79,6 +79,8 @@ static ChunkPlan matrix_plan(kb_engine *e, uint32_t t0, uint32_t n, uint32_t fit
   p.r.mrow_task0 = t0;
   return p;
 }
+static constexpr uint32_t KB_XCHUNK_GRID_Y = 65535u;   // chunks per expansion launch (the largest grid y)
+static uint32_t expand_launches(const ChunkPlan &p) { return p.direct ? 0u : (p.n_xchunks + KB_XCHUNK_GRID_Y - 1) / KB_XCHUNK_GRID_Y; }
 static void matrix_launch(kb_engine *e, const ChunkPlan &p, uint32_t n, uint32_t k) {
   ensure_ip_scratch(e, p.direct ? n : p.ns);
   if (p.direct) {
@@ -96,7 +98,11 @@ static void matrix_launch(kb_engine *e, const ChunkPlan &p, uint32_t n, uint32_t
   // round 6: the TILED expansion — a workgroup loads its tile of the shape row once for 64 task rows, the rows in shape order.  (Round 5's copy, one
   // workgroup per task row, re-fetched the shape rows through eight L2s — 1.25 x the algorithmic bytes against 1.04 x — and was slower at R = 16 and at
   // 1M x 50k on every box, within +- 6 % at 100k x 10k depending on the box: profiles/round6/call8..., call10..., call12...; retired with its switch.)
-  kb_launch_expand(e->dev, p.rs.score, p.rs.maskw, e->b_xslot.as<uint32_t>(), e->b_xorder.as<uint32_t>(), n, p.r.score, p.r.maskw, e->stream, e->b_xchunks.as<KbXChunk>(), p.n_xchunks);
+  // the chunk index is k_expand_tiles' grid y, which HIP caps at 65 535: a plan with more chunks (a whole-range plan of ~850 000 rows or more in many
+  // small shapes, kb_bench_matrix / KB_EVAL_MATRIX_ROWS) is launched in slices of the chunk table; a chunk names its own stretch of `order`
+  for (uint32_t c0 = 0; c0 < p.n_xchunks; c0 += KB_XCHUNK_GRID_Y)
+    kb_launch_expand(e->dev, p.rs.score, p.rs.maskw, e->b_xslot.as<uint32_t>(), e->b_xorder.as<uint32_t>(), n, p.r.score, p.r.maskw, e->stream,
+                     e->b_xchunks.as<KbXChunk>() + c0, std::min<uint32_t>(KB_XCHUNK_GRID_Y, p.n_xchunks - c0));
   if (k) kb_launch_argmax(e->dev, p.r, e->stream);
 }
 static KbRound matrix_chunk(kb_engine *e, uint32_t t0, uint32_t n, uint32_t fit_mode, uint32_t k) {
@@ -112,10 +118,18 @@ int kb_eval_matrix(kb_engine *e, uint32_t t0, uint32_t t1, uint32_t fit_mode, ui
     if (t0 > t1 || t1 > e->hs.T) throw EngineError(KB_E_INVALID, "row range out of bounds");
     const uint32_t N = e->hs.N, NP = e->dev.NP;
     const size_t rowb = ((size_t)N + 7) / 8;
-    const uint32_t chunk = 4096;
-    for (uint32_t a = t0; a < t1; a += chunk) {
+    // KB_EVAL_MATRIX_ROWS=<n>: rows per plan (default 4096; a test hook: a value >= the range plans it whole, as kb_bench_matrix does).
+    // While it is set, every plan is described on stderr (its shapes, expansion chunks and launches), so a test can tell which path it took.
+    const char *kv = getenv("KB_EVAL_MATRIX_ROWS");
+    const unsigned long long kn = kv ? strtoull(kv, nullptr, 10) : 0ull;
+    const uint32_t chunk = kn ? (uint32_t)std::min<unsigned long long>(kn, 0xFFFFFFFFull) : 4096u;
+    for (uint32_t a = t0; a < t1; a += std::min(chunk, t1 - a)) {
       uint32_t n = std::min(chunk, t1 - a);
-      matrix_chunk(e, a, n, fit_mode, 0);
+      ChunkPlan p = matrix_plan(e, a, n, fit_mode, 0);
+      matrix_launch(e, p, n, 0);
+      if (kv)
+        fprintf(stderr, "kb_eval_matrix: plan rows %u..%u shapes %u direct %d expansion chunks %u launches %u\n", a, a + n, p.ns, p.direct ? 1 : 0,
+                p.n_xchunks, expand_launches(p));
       if (score)
         HIP_OK(hipMemcpy2DAsync(score + (size_t)(a - t0) * N, sizeof(uint16_t) * N, e->b_score.p, sizeof(uint16_t) * NP, sizeof(uint16_t) * N, n,
                                 hipMemcpyDeviceToHost, e->stream));

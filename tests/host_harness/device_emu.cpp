@@ -627,17 +627,22 @@ void kb_launch_repair(const KbDev &d, const KbRound &r, void *stream) {
 
 void kb_launch_expand(const KbDev &d, const uint16_t *s_score, const uint32_t *s_mask, const uint32_t *row_slot, const uint32_t *order, uint32_t n_rows,
                       uint16_t *score, uint32_t *maskw, void *stream, const KbXChunk *chunks, uint32_t n_chunks) {
-  if (chunks) {   // the chunk table's contract: the chunks tile `order` (or, without it, the rows) exactly, every row of a chunk has the chunk's shape (the kernel takes the shape from the chunk)
-    kbemu_enqueue((hipStream_t)stream, [row_slot, order, n_rows, chunks, n_chunks]() {
-      uint32_t at = 0;
+  if (chunks) {   // the chunk table's contract: a launch's chunks are consecutive stretches of `order` (or, without it, of the rows), every row of a chunk has the
+                  // chunk's shape (the kernel takes the shape from the chunk); a plan of more than 65 535 chunks comes in several launches (kb_matrix.cpp)
+    kbemu_enqueue((hipStream_t)stream, [d, s_score, s_mask, row_slot, order, n_rows, score, maskw, chunks, n_chunks]() {
+      uint32_t at = n_chunks ? chunks[0].first : 0u;
       for (uint32_t c = 0; c < n_chunks; c++) {
-        if (chunks[c].first != at || chunks[c].count == 0 || chunks[c].count > KB_XCHUNK_ROWS) abort();
-        for (uint32_t i = 0; i < chunks[c].count; i++)
-          if (row_slot[order ? order[at + i] : at + i] != chunks[c].slot) abort();   // (no `order`: the chunks tile the rows themselves)
+        if (chunks[c].first != at || chunks[c].count == 0 || chunks[c].count > KB_XCHUNK_ROWS || at + chunks[c].count > n_rows) abort();
+        for (uint32_t i = 0; i < chunks[c].count; i++) {   // the kernel writes exactly the rows of its chunks
+          const uint32_t row = order ? order[at + i] : at + i;
+          if (row >= n_rows || row_slot[row] != chunks[c].slot) abort();
+          std::memcpy(score + (size_t)row * d.NP, s_score + (size_t)chunks[c].slot * d.NP, sizeof(uint16_t) * d.NP);
+          std::memcpy(maskw + (size_t)row * (d.NP / 32), s_mask + (size_t)chunks[c].slot * (d.NP / 32), sizeof(uint32_t) * (d.NP / 32));
+        }
         at += chunks[c].count;
       }
-      if (at != n_rows) abort();
     });
+    return;
   }
   kbemu_enqueue((hipStream_t)stream, [d, s_score, s_mask, row_slot, order, n_rows, score, maskw]() {
   for (uint32_t at = 0; at < n_rows; at++) {   // the contract: `order` is a permutation of the rows (the kernel takes them in that order)

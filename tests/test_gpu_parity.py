@@ -119,8 +119,9 @@ def test_matrix_parity_r16_and_after_allocate(oracle_mod):
 @pytest.mark.parametrize("n_res,diverse", [(2, False), (2, True), (16, False)])
 def test_matrix_parity_wide_direct_tiles(oracle_mod, n_res, diverse):
     """A matrix wide and tall enough (4 608 rows x 9 000 nodes) for the tiles the small configurations never launch: k_matrix_runs (runs of
-    adjacent equal rows evaluated once, streamed out with 16-byte stores; rows [0, 4096) and the ragged rest), k_matrix<4, 32>
-    (KB_MATRIX_NO_DEDUP), and the per-shape + expansion path, all bit-equal to the oracle — also in a live state after an allocate pass."""
+    adjacent equal rows evaluated once, streamed out with 16-byte stores; rows [0, 4096) and the ragged rest), the same tile without sharing
+    (KB_MATRIX_NO_DEDUP clears its row flags; k_matrix<4, 32> is the per-shape launch of tens of thousands of shapes, tests/test_gpu_kernel_edges.py),
+    and the per-shape + expansion path, all bit-equal to the oracle — also in a live state after an allocate pass."""
     p = snapmod.SynthParams(n_tasks=5000, n_nodes=9000, n_queues=8, n_res=n_res, seed=snapmod.SEED_BASE + 77 + n_res)
     p.diverse_requests = diverse
     snap = snapmod.synth(p)
