@@ -1,6 +1,7 @@
 // kb_host.hpp — host-side model of the session for the engine: api.Resource algebra with map-presence
-// semantics, plugin OnSessionOpen state (drf totals, proportion deserved), and the order machine that
-// reproduces the control flow of allocate.go:43-194 around the device rounds.
+// semantics, plugin OnSessionOpen state (drf totals, proportion deserved), the plugin order rules and
+// container/heap that both host machines use, and the order machine that reproduces the control flow of
+// allocate.go:43-194 around the device rounds.
 //
 // This is the engine's own implementation (C++), independent of oracle/kb_oracle.c (test infrastructure).
 #pragma once
@@ -121,6 +122,122 @@ struct HostSession {
   std::vector<int32_t> job_ready;          // [J] ReadyTaskNum
 };
 
+// ---- the plugin rules both host machines order by: the order machine (allocate / backfill, kb_order.cpp) and the evict machine
+// (preempt / reclaim, kb_preempt.cpp) pass their own running aggregates ----
+
+// session_plugins.go:298-331 TaskOrderFn + priority.go:40-56, then pod creation time, then UID (== canonical index order)
+inline bool task_order_less(const Policy &pol, const HostSession &hs, uint32_t l, uint32_t r) {
+  if (pol.task_order_priority && hs.t_prio[l] != hs.t_prio[r]) return hs.t_prio[l] > hs.t_prio[r];
+  if (hs.t_creation[l] != hs.t_creation[r]) return hs.t_creation[l] < hs.t_creation[r];
+  return l < r;
+}
+
+// session_plugins.go:243-267 JobOrderFn + priority.go:61-77, gang.go:96-119, drf.go:114-130, then creation time, then UID.
+// `ready(j)`: job j's ReadyTaskNum
+template <typename Ready>
+inline bool job_order_less(const Policy &pol, const HostSession &hs, const std::vector<double> &jshare, Ready ready, uint32_t l, uint32_t r) {
+  for (uint8_t p : pol.job_chain) {
+    int j = 0;
+    if (p == KB_PLUGIN_PRIORITY) {
+      if (hs.job_prio[l] > hs.job_prio[r]) j = -1;
+      else if (hs.job_prio[l] < hs.job_prio[r]) j = 1;
+    } else if (p == KB_PLUGIN_GANG) {
+      bool lr = ready(l) >= hs.job_min[l], rr = ready(r) >= hs.job_min[r];
+      if (lr && rr) j = 0; else if (lr) j = 1; else if (rr) j = -1;
+    } else if (p == KB_PLUGIN_DRF) {
+      if (jshare[l] == jshare[r]) j = 0; else if (jshare[l] < jshare[r]) j = -1; else j = 1;
+    }
+    if (j != 0) return j < 0;
+  }
+  if (hs.job_creation[l] == hs.job_creation[r]) return l < r;
+  return hs.job_creation[l] < hs.job_creation[r];
+}
+
+// session_plugins.go:270-295 QueueOrderFn + proportion.go:156-169, then creation time, then UID
+inline bool queue_order_less(const Policy &pol, const HostSession &hs, const std::vector<double> &qshare, uint32_t l, uint32_t r) {
+  if (pol.queue_order_proportion) {
+    const double ls = qshare[l], rs = qshare[r];
+    if (!(ls == rs)) return ls < rs;
+  }
+  if (hs.queue_creation[l] == hs.queue_creation[r]) return l < r;
+  return hs.queue_creation[l] < hs.queue_creation[r];
+}
+
+// The allocated rows below are dense: `mask` bit (d-2) <=> scalar key d is present, and a row holds 0 at every absent key.  A caller that
+// keeps no masks (the order machine) passes kEveryKey: an absent key reads 0 either way.
+constexpr uint32_t kEveryKey = ~0u;
+
+// session_plugins.go:165-179 Overused + proportion.go:198-209: deserved.LessEqual(allocated) (res_less_equal) against row `alloc`.
+// LessEqual's nil-map early-outs need no test of their own: a nil `deserved` has no scalar key to compare, and a nil `allocated` returns
+// false exactly where the compare against its absent key's 0 fails — only keys above kMinMilliScalar are compared, and none of those is
+// within kMinMilliScalar of 0.  So kEveryKey on a dense row gives the answer of the row's real key set.
+inline bool queue_overused(const Policy &pol, const HostSession &hs, const double *alloc, uint32_t mask, uint32_t q) {
+  if (!pol.has_proportion) return false;
+  const Res &des = hs.deserved[q];
+  if (!le_func(des.v[0], alloc[0], kMinMilliCPU)) return false;
+  if (!le_func(des.v[1], alloc[1], kMinMemory)) return false;
+  for (int d = 2; d < hs.R; d++) {
+    if (!des.has(d) || des.v[d] <= kMinMilliScalar) continue;
+    if (!le_func(des.v[d], ((mask >> (d - 2)) & 1u) ? alloc[d] : 0.0, kMinMilliScalar)) return false;
+  }
+  return true;
+}
+
+// drf.go:157-171 calculateShare (of = drf.totalResource) and proportion.go:241-253 updateShare (of = the queue's deserved): the largest
+// helpers.Share(allocated.Get(rn), of.Get(rn)) over of.ResourceNames(), against row `alloc`
+inline double dominant_share(const Res &of, const double *alloc, uint32_t mask, int R) {
+  double share = 0;
+  for (int d = 0; d < R; d++) {
+    if (d >= 2 && !of.has(d)) continue;
+    const double s = helpers_share((d < 2 || ((mask >> (d - 2)) & 1u)) ? alloc[d] : 0.0, of.get(d));
+    if (s > share) share = s;
+  }
+  return share;
+}
+
+// ---- container/heap (util/priority_queue.go:26-94 wraps it) ----
+// Both machines keep heaps whose keys move while items sit in them (allocate.go:50-52 pushes one queue entry PER JOB, so the same queue
+// sits in the heap many times while its share mutates; a job's gang readiness and drf share move as its tasks are handled), so the pop
+// order depends on the sift mechanics:
+//   Push: append, up(n-1);  Pop: swap(0,n-1), down(0,n-1), remove last
+//   up(j):   i=(j-1)/2; stop if i==j or !less(j,i); swap; j=i
+//   down(i): j1=2i+1; stop if j1>=n; j=j1; if j1+1<n && less(j1+1,j1) j=j1+1; stop if !less(j,i); swap; i=j
+// The sifts below move a hole instead of swapping (the element on its way is compared by value, the others move one level): the same
+// comparisons in the same order as container/heap's up / down, the same final array, half the writes.  `h[0, n)` is the heap before the
+// call; every write goes through `set(slot, value)`, so that the order machine's roll-back journals see each one.
+
+// Push: x becomes item n
+template <typename Less, typename Set>
+inline void go_heap_push(const uint32_t *h, uint32_t n, uint32_t x, Less less, Set set) {
+  uint32_t j = n;
+  while (j > 0) {
+    const uint32_t i = (j - 1) / 2;
+    if (!less(x, h[i])) break;
+    set(j, h[i]);
+    j = i;
+  }
+  set(j, x);
+}
+// Pop (n >= 1): returns the old root; the heap is h[0, n-1) afterwards (the last element sinks from the root)
+template <typename Less, typename Set>
+inline uint32_t go_heap_pop(const uint32_t *h, uint32_t n, Less less, Set set) {
+  const uint32_t top = h[0];
+  if (--n == 0) return top;
+  const uint32_t x = h[n];
+  uint32_t i = 0;
+  for (;;) {
+    const uint32_t j1 = 2 * i + 1;
+    if (j1 >= n) break;
+    uint32_t j = j1;
+    if (j1 + 1 < n && less(h[j1 + 1], h[j1])) j = j1 + 1;
+    if (!less(h[j], x)) break;
+    set(i, h[j]);
+    i = j;
+  }
+  set(i, x);
+  return top;
+}
+
 // kb_session.cpp: the host half of kb_engine_create / kb_session_load (no device code; also built into the CPU test harnesses)
 Policy compile_policy(const kb_config *cfg);
 void build_host_session(const kb_snapshot *sn, const Policy &pol, uint32_t NP, HostSession &hs, std::vector<uint32_t> &t_active, std::vector<uint32_t> &nmask);
@@ -226,9 +343,8 @@ class OrderMachine {
   }
 
   bool job_ready(uint32_t j) const { return pol_->gang_job_ready ? ready[j] >= hs_->job_min[j] : true; }
-  bool queue_less(uint32_t l, uint32_t r) const;
-  bool job_less(uint32_t l, uint32_t r) const;
-  bool overused(uint32_t q) const;
+  bool queue_less(uint32_t l, uint32_t r) const { return queue_order_less(*pol_, *hs_, qshare, l, r); }
+  bool job_less(uint32_t l, uint32_t r) const { return job_order_less(*pol_, *hs_, jshare, [this](uint32_t j) { return ready[j]; }, l, r); }
   void qpush(uint32_t q);
   uint32_t qpop();
   void jpush(uint32_t q, uint32_t j);

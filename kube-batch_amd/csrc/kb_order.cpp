@@ -1,121 +1,25 @@
-// kb_order.cpp — the order machine: queue / job / task ordering of allocate.go around the device rounds.
-//
-// Heaps follow Go's container/heap exactly (util/priority_queue.go:26-94 wraps it): the queue heap holds one entry
-// PER JOB (allocate.go:50-52), so the same queue sits in it many times while its share mutates, and the pop order
-// then depends on the sift mechanics:
-//   Push: append, up(n-1);  Pop: swap(0,n-1), down(0,n-1), remove last
-//   up(j):   i=(j-1)/2; stop if i==j or !less(j,i); swap; j=i
-//   down(i): j1=2i+1; stop if j1>=n; j=j1; if j1+1<n && less(j1+1,j1) j=j1+1; stop if !less(j,i); swap; i=j
+// kb_order.cpp — the order machine: queue / job / task ordering of allocate.go around the device rounds.  The plugin rules it orders
+// by and the container/heap sifts are kb_host.hpp's, shared with the evict machine.
 #include "kb_host.hpp"
 
 namespace kb {
 
-// session_plugins.go:270-295 + proportion.go:156-169
-bool OrderMachine::queue_less(uint32_t l, uint32_t r) const {
-  if (pol_->queue_order_proportion) {
-    double ls = qshare[l], rs = qshare[r];
-    if (!(ls == rs)) return ls < rs;
-  }
-  if (hs_->queue_creation[l] == hs_->queue_creation[r]) return l < r;   // UID order == canonical index order
-  return hs_->queue_creation[l] < hs_->queue_creation[r];
-}
-
-// session_plugins.go:243-267 + priority.go:61-77, gang.go:96-119, drf.go:114-130
-bool OrderMachine::job_less(uint32_t l, uint32_t r) const {
-  for (uint8_t p : pol_->job_chain) {
-    int j = 0;
-    if (p == KB_PLUGIN_PRIORITY) {
-      if (hs_->job_prio[l] > hs_->job_prio[r]) j = -1;
-      else if (hs_->job_prio[l] < hs_->job_prio[r]) j = 1;
-    } else if (p == KB_PLUGIN_GANG) {
-      bool lr = ready[l] >= hs_->job_min[l], rr = ready[r] >= hs_->job_min[r];
-      if (lr && rr) j = 0; else if (lr) j = 1; else if (rr) j = -1;
-    } else if (p == KB_PLUGIN_DRF) {
-      if (jshare[l] == jshare[r]) j = 0; else if (jshare[l] < jshare[r]) j = -1; else j = 1;
-    }
-    if (j != 0) return j < 0;
-  }
-  if (hs_->job_creation[l] == hs_->job_creation[r]) return l < r;
-  return hs_->job_creation[l] < hs_->job_creation[r];
-}
-
-// session_plugins.go:165-179 + proportion.go:198-209: deserved.LessEqual(allocated)
-bool OrderMachine::overused(uint32_t q) const {
-  if (!pol_->has_proportion) return false;
-  const int R = hs_->R;
-  const Res &des = hs_->deserved[q];
-  const double *al = &qalloc[(size_t)q * R];
-  if (!le_func(des.v[0], al[0], kMinMilliCPU)) return false;
-  if (!le_func(des.v[1], al[1], kMinMemory)) return false;
-  for (int d = 2; d < R; d++) {
-    if (!des.has(d) || des.v[d] <= kMinMilliScalar) continue;
-    // an absent key on the right reads 0 and a nil map fails exactly when the compare against 0 fails
-    if (!le_func(des.v[d], al[d], kMinMilliScalar)) return false;
-  }
-  return true;
-}
-
-// The sifts move a hole instead of swapping (the element on its way is compared by value, the others move one level): the same comparisons in
-// the same order as container/heap's up / down, the same final array, half the writes.
+// the queue heap and the per-queue job heaps: every write goes through qset / jset, so the roll-back journals see it
 void OrderMachine::qpush(uint32_t q) {
-  uint32_t j = qn_++;
-  while (j > 0) {
-    const uint32_t i = (j - 1) / 2;
-    if (!queue_less(q, qheap_[i])) break;
-    qset(j, qheap_[i]);
-    j = i;
-  }
-  qset(j, q);
+  go_heap_push(qheap_.data(), qn_++, q, [this](uint32_t l, uint32_t r) { return queue_less(l, r); }, [this](uint32_t i, uint32_t v) { qset(i, v); });
 }
 uint32_t OrderMachine::qpop() {
-  const uint32_t n = --qn_;          // Pop: swap(0, n), down(0, n), remove last — the old root leaves, the last element sinks from the root
-  const uint32_t top = qheap_[0];
-  if (n == 0) return top;
-  const uint32_t x = qheap_[n];
-  uint32_t i = 0;
-  for (;;) {
-    const uint32_t j1 = 2 * i + 1;
-    if (j1 >= n) break;
-    uint32_t j = j1;
-    if (j1 + 1 < n && queue_less(qheap_[j1 + 1], qheap_[j1])) j = j1 + 1;
-    if (!queue_less(qheap_[j], x)) break;
-    qset(i, qheap_[j]);
-    i = j;
-  }
-  qset(i, x);
-  return top;
+  return go_heap_pop(qheap_.data(), qn_--, [this](uint32_t l, uint32_t r) { return queue_less(l, r); }, [this](uint32_t i, uint32_t v) { qset(i, v); });
 }
 void OrderMachine::jpush(uint32_t q, uint32_t job) {
   const uint32_t b = jheap_off_[q];
-  const uint32_t *h = &jheap_items_[b];
-  uint32_t j = jheap_n_[q]++;
-  while (j > 0) {
-    const uint32_t i = (j - 1) / 2;
-    if (!job_less(job, h[i])) break;
-    jset(b + j, h[i]);
-    j = i;
-  }
-  jset(b + j, job);
+  go_heap_push(&jheap_items_[b], jheap_n_[q]++, job, [this](uint32_t l, uint32_t r) { return job_less(l, r); },
+               [this, b](uint32_t i, uint32_t v) { jset(b + i, v); });
 }
 uint32_t OrderMachine::jpop(uint32_t q) {
   const uint32_t b = jheap_off_[q];
-  const uint32_t *h = &jheap_items_[b];
-  const uint32_t n = --jheap_n_[q];
-  const uint32_t top = h[0];
-  if (n == 0) return top;
-  const uint32_t x = h[n];
-  uint32_t i = 0;
-  for (;;) {
-    const uint32_t j1 = 2 * i + 1;
-    if (j1 >= n) break;
-    uint32_t j = j1;
-    if (j1 + 1 < n && job_less(h[j1 + 1], h[j1])) j = j1 + 1;
-    if (!job_less(h[j], x)) break;
-    jset(b + i, h[j]);
-    i = j;
-  }
-  jset(b + i, x);
-  return top;
+  return go_heap_pop(&jheap_items_[b], jheap_n_[q]--, [this](uint32_t l, uint32_t r) { return job_less(l, r); },
+                     [this, b](uint32_t i, uint32_t v) { jset(b + i, v); });
 }
 
 void OrderMachine::init_allocate(const HostSession *hs, const Policy *pol) {
@@ -181,20 +85,16 @@ void OrderMachine::build_jobs(uint32_t q) {
   for (uint32_t k = jheap_off_[q]; k < jheap_off_[q + 1]; k++) jpush(q, qjobs_[k]);
 }
 
-// session_plugins.go:298-331 TaskOrderFn: priority plugin, then pod creation time, then UID; the comparator is a strict total order over
-// immutable keys, so the heap's pop order (allocate.go:110-123 pushes into a PriorityQueue) is the sorted order
+// TaskOrderFn (task_order_less) is a strict total order over immutable keys, so the heap's pop order (allocate.go:110-123 pushes into a
+// PriorityQueue) is the sorted order
 void OrderMachine::build_pending(uint32_t j) {
-  const HostSession *hs = hs_;
-  const uint32_t b = hs->job_begin[j];
+  const HostSession &hs = *hs_;
+  const Policy &pol = *pol_;
+  const uint32_t b = hs.job_begin[j];
   uint32_t n = b;
-  for (uint32_t t = b; t < hs->job_begin[j + 1]; t++)
-    if (hs->t_status[t] == KB_TASK_PENDING && !hs->t_res_empty[t]) pend_[n++] = t;
-  const bool by_prio = pol_->task_order_priority;
-  std::sort(pend_.begin() + b, pend_.begin() + n, [hs, by_prio](uint32_t l, uint32_t r) {
-    if (by_prio && hs->t_prio[l] != hs->t_prio[r]) return hs->t_prio[l] > hs->t_prio[r];
-    if (hs->t_creation[l] != hs->t_creation[r]) return hs->t_creation[l] < hs->t_creation[r];
-    return l < r;
-  });
+  for (uint32_t t = b; t < hs.job_begin[j + 1]; t++)
+    if (hs.t_status[t] == KB_TASK_PENDING && !hs.t_res_empty[t]) pend_[n++] = t;
+  std::sort(pend_.begin() + b, pend_.begin() + n, [&](uint32_t l, uint32_t r) { return task_order_less(pol, hs, l, r); });
   pend_end_[j] = n;
   pend_built_[j] = 1;
 }
@@ -274,7 +174,7 @@ bool OrderMachine::next(uint32_t &task) {
     }
     if (qn_ == 0) return false;              // allocate.go:90-92
     uint32_t q = qpop();
-    if (overused(q)) continue;               // allocate.go:95-98
+    if (queue_overused(*pol_, *hs_, &qalloc[(size_t)q * hs_->R], kEveryKey, q)) continue;   // allocate.go:95-98 (dense rows)
     if (jheap_n_[q] == kNotBuilt) build_jobs(q);
     if (jheap_n_[q] == 0) continue;          // allocate.go:104-107
     uint32_t j = jpop(q);
@@ -284,34 +184,23 @@ bool OrderMachine::next(uint32_t &task) {
   }
 }
 
-// drf.go:135-145 and proportion.go:212-223 AllocateFunc (fired by ssn.Allocate and ssn.Pipeline alike)
+// drf.go:135-145 and proportion.go:212-223 AllocateFunc (fired by ssn.Allocate and ssn.Pipeline alike) on the dense rows
 void OrderMachine::update_shares(uint32_t j, uint32_t t) {
   const int R = hs_->R;
   const double *tr = &hs_->t_res_rows[(size_t)t * R];   // absent scalar keys hold 0.0
   const uint32_t tmask = hs_->t_resmask[t];
   if (pol_->has_drf) {
     double *a = &jalloc[(size_t)j * R];
-    double share = 0;
-    for (int d = 0; d < R; d++) {
+    for (int d = 0; d < R; d++)
       if (d < 2 || ((tmask >> (d - 2)) & 1u)) a[d] += tr[d];
-      if (d >= 2 && !hs_->total.has(d)) continue;
-      double s = helpers_share(a[d], hs_->total.get(d));
-      if (s > share) share = s;
-    }
-    jshare[j] = share;
+    jshare[j] = dominant_share(hs_->total, a, kEveryKey, R);
   }
   if (pol_->has_proportion) {
-    uint32_t q = hs_->job_queue[j];
+    const uint32_t q = hs_->job_queue[j];
     double *a = &qalloc[(size_t)q * R];
-    const Res &des = hs_->deserved[q];
-    double share = 0;
-    for (int d = 0; d < R; d++) {
+    for (int d = 0; d < R; d++)
       if (d < 2 || ((tmask >> (d - 2)) & 1u)) a[d] += tr[d];
-      if (d >= 2 && !des.has(d)) continue;
-      double s = helpers_share(a[d], des.get(d));
-      if (s > share) share = s;
-    }
-    qshare[q] = share;
+    qshare[q] = dominant_share(hs_->deserved[q], a, kEveryKey, R);
   }
 }
 

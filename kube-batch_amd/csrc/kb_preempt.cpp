@@ -10,8 +10,8 @@ namespace kb {
 
 namespace {
 
-// container/heap with Go's sift mechanics (util/priority_queue.go:26-94 wraps it): the job heap's keys (gang readiness, drf share)
-// move while jobs sit in it, so the pop order depends on them
+// container/heap (kb_host.hpp: go_heap_push / go_heap_pop) on a vector: the job heap's keys (gang readiness, drf share) move while jobs
+// sit in it, so the pop order depends on Go's sift mechanics
 template <typename Less> struct GoHeap {
   std::vector<uint32_t> a;
   Less less;
@@ -19,30 +19,12 @@ template <typename Less> struct GoHeap {
   bool empty() const { return a.empty(); }
   void push(uint32_t x) {
     a.push_back(x);
-    size_t j = a.size() - 1;
-    for (;;) {
-      size_t i = j == 0 ? 0 : (j - 1) / 2;
-      if (i == j || !less(a[j], a[i])) break;
-      std::swap(a[i], a[j]);
-      j = i;
-    }
+    go_heap_push(a.data(), (uint32_t)a.size() - 1, x, less, [this](uint32_t i, uint32_t v) { a[i] = v; });
   }
   uint32_t pop() {
-    size_t n = a.size() - 1;
-    std::swap(a[0], a[n]);
-    size_t i = 0;
-    for (;;) {
-      size_t j1 = 2 * i + 1;
-      if (j1 >= n) break;
-      size_t j = j1;
-      if (j1 + 1 < n && less(a[j1 + 1], a[j1])) j = j1 + 1;
-      if (!less(a[j], a[i])) break;
-      std::swap(a[i], a[j]);
-      i = j;
-    }
-    uint32_t x = a.back();
+    const uint32_t top = go_heap_pop(a.data(), (uint32_t)a.size(), less, [this](uint32_t i, uint32_t v) { a[i] = v; });
     a.pop_back();
-    return x;
+    return top;
   }
 };
 
@@ -96,38 +78,6 @@ bool PreemptMachine::job_pipelined(uint32_t j) const {   // session_plugins.go:2
   if (!pol_->gang_job_pipelined) return true;
   return cnt[(size_t)j * 10 + KB_TASK_PIPELINED] + ready_num(j) >= hs_->job_min[j];
 }
-bool PreemptMachine::job_less(uint32_t l, uint32_t r) const {   // session_plugins.go:243-267 + priority.go:61-77, gang.go:96-119, drf.go:114-130
-  for (uint8_t p : pol_->job_chain) {
-    int j = 0;
-    if (p == KB_PLUGIN_PRIORITY) {
-      if (hs_->job_prio[l] > hs_->job_prio[r]) j = -1;
-      else if (hs_->job_prio[l] < hs_->job_prio[r]) j = 1;
-    } else if (p == KB_PLUGIN_GANG) {
-      bool lr = ready_num(l) >= hs_->job_min[l], rr = ready_num(r) >= hs_->job_min[r];
-      if (lr && rr) j = 0; else if (lr) j = 1; else if (rr) j = -1;
-    } else if (p == KB_PLUGIN_DRF) {
-      if (jshare[l] == jshare[r]) j = 0; else if (jshare[l] < jshare[r]) j = -1; else j = 1;
-    }
-    if (j != 0) return j < 0;
-  }
-  if (hs_->job_creation[l] == hs_->job_creation[r]) return l < r;
-  return hs_->job_creation[l] < hs_->job_creation[r];
-}
-bool PreemptMachine::task_less(uint32_t l, uint32_t r) const {   // session_plugins.go:298-331 + priority.go:40-56
-  if (pol_->task_order_priority && hs_->t_prio[l] != hs_->t_prio[r]) return hs_->t_prio[l] > hs_->t_prio[r];
-  if (hs_->t_creation[l] != hs_->t_creation[r]) return hs_->t_creation[l] < hs_->t_creation[r];
-  return l < r;
-}
-double PreemptMachine::drf_share(const double *alloc, uint32_t mask) const {   // drf.go:157-171
-  double share = 0;
-  for (int d = 0; d < hs_->R; d++) {
-    if (d >= 2 && !hs_->total.has(d)) continue;
-    const double a = (d < 2 || ((mask >> (d - 2)) & 1u)) ? alloc[d] : 0.0;
-    const double s = helpers_share(a, hs_->total.get(d));
-    if (s > share) share = s;
-  }
-  return share;
-}
 
 // drf.go:135-156, proportion.go:212-235: AllocateFunc / DeallocateFunc (fired by Evict, Pipeline and their undo)
 void PreemptMachine::fire_allocate(uint32_t t) {
@@ -138,7 +88,7 @@ void PreemptMachine::fire_allocate(uint32_t t) {
     for (int d = 0; d < R; d++)
       if (d < 2 || ((tm >> (d - 2)) & 1u)) a[d] += hs_->t_res[(size_t)d * hs_->T + t];
     jmask[j] |= tm;
-    jshare[j] = drf_share(a, jmask[j]);
+    jshare[j] = dominant_share(hs_->total, a, jmask[j], R);
   }
   if (pol_->has_proportion && hs_->job_queue[j] < hs_->Q) {
     const uint32_t q = hs_->job_queue[j];
@@ -146,14 +96,7 @@ void PreemptMachine::fire_allocate(uint32_t t) {
     for (int d = 0; d < R; d++)
       if (d < 2 || ((tm >> (d - 2)) & 1u)) a[d] += hs_->t_res[(size_t)d * hs_->T + t];
     qmask[q] |= tm;
-    const Res &des = hs_->deserved[q];
-    double share = 0;
-    for (int d = 0; d < R; d++) {
-      if (d >= 2 && !des.has(d)) continue;
-      const double s = helpers_share((d < 2 || ((qmask[q] >> (d - 2)) & 1u)) ? a[d] : 0.0, des.get(d));
-      if (s > share) share = s;
-    }
-    qshare[q] = share;
+    qshare[q] = dominant_share(hs_->deserved[q], a, qmask[q], R);
   }
   counted[t] = 1;
 }
@@ -172,20 +115,13 @@ void PreemptMachine::fire_deallocate(uint32_t t) {
   if (pol_->has_drf) {
     double *a = &jalloc[(size_t)j * R];
     sub(a, jmask[j]);
-    jshare[j] = drf_share(a, jmask[j]);
+    jshare[j] = dominant_share(hs_->total, a, jmask[j], R);
   }
   if (pol_->has_proportion && hs_->job_queue[j] < hs_->Q) {
     const uint32_t q = hs_->job_queue[j];
     double *a = &qalloc[(size_t)q * R];
     sub(a, qmask[q]);
-    const Res &des = hs_->deserved[q];
-    double share = 0;
-    for (int d = 0; d < R; d++) {
-      if (d >= 2 && !des.has(d)) continue;
-      const double s = helpers_share((d < 2 || ((qmask[q] >> (d - 2)) & 1u)) ? a[d] : 0.0, des.get(d));
-      if (s > share) share = s;
-    }
-    qshare[q] = share;
+    qshare[q] = dominant_share(hs_->deserved[q], a, qmask[q], R);
   }
   counted[t] = 0;
 }
@@ -482,7 +418,7 @@ size_t PreemptMachine::evictable(uint32_t preemptor, const std::vector<uint32_t>
         lalloc.mask = jmask[pj];
         for (int d = 0; d < R; d++) lalloc.v[d] = jalloc[(size_t)pj * R + d];
         res_add(lalloc, task_res(preemptor), R);
-        const double ls = drf_share(lalloc.v, lalloc.mask);
+        const double ls = dominant_share(hs_->total, lalloc.v, lalloc.mask, R);
         std::vector<uint32_t> &ajob = scratch_ids_;
         std::vector<Res> &alloc = scratch_alloc_;
         ajob.clear(); alloc.clear();
@@ -498,7 +434,7 @@ size_t PreemptMachine::evictable(uint32_t preemptor, const std::vector<uint32_t>
             alloc.push_back(r);
           }
           if (!res_sub(alloc[a], task_res(pre[i]), R)) throw EngineError(KB_E_UNSUPPORTED, "preempt: drf allocation would underflow (the reference panics in Resource.Sub)");
-          const double rs = drf_share(alloc[a].v, alloc[a].mask);
+          const double rs = dominant_share(hs_->total, alloc[a].v, alloc[a].mask, R);
           keep[i] = (ls < rs) || (std::fabs(ls - rs) <= 0.000001);   // shareDelta (drf.go:33)
         }
       } else {
@@ -852,24 +788,6 @@ void PreemptMachine::run() {
   }
 }
 
-// session_plugins.go:270-295 + proportion.go:156-169
-bool PreemptMachine::queue_less(uint32_t l, uint32_t r) const {
-  if (pol_->queue_order_proportion) {
-    const double ls = qshare[l], rs = qshare[r];
-    if (!(ls == rs)) return ls < rs;
-  }
-  if (hs_->queue_creation[l] == hs_->queue_creation[r]) return l < r;
-  return hs_->queue_creation[l] < hs_->queue_creation[r];
-}
-// session_plugins.go:165-179 + proportion.go:198-209: deserved.LessEqual(allocated)
-bool PreemptMachine::overused(uint32_t q) const {
-  if (!pol_->has_proportion) return false;
-  Res a;
-  a.mask = qmask[q];
-  for (int d = 0; d < hs_->R; d++) a.v[d] = qalloc[(size_t)q * hs_->R + d];
-  return res_less_equal(hs_->deserved[q], a, hs_->R);
-}
-
 // reclaimAction.Execute (reclaim.go:41-193).  Canonical orders where the reference ranges over Go maps: jobs ascending JobID,
 // nodes ascending name, a node's tasks ascending task index.
 void PreemptMachine::run_reclaim() {
@@ -897,7 +815,7 @@ void PreemptMachine::run_reclaim() {
   for (;;) {
     if (queues.empty()) break;
     const uint32_t q = queues.pop();
-    if (overused(q)) continue;             // reclaim.go:96-99
+    if (queue_overused(*pol_, *hs_, &qalloc[(size_t)q * R], qmask[q], q)) continue;   // reclaim.go:96-99
     if (qjobs[q].empty()) continue;        // :102-106
     const uint32_t j = qjobs[q].pop();
     if (jtasks.empty(j)) continue;         // :109-113

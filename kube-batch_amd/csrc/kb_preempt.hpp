@@ -120,9 +120,9 @@ class PreemptMachine {
   Res task_init(uint32_t t) const;
   int ready_num(uint32_t j) const;
   bool job_pipelined(uint32_t j) const;
-  bool job_less(uint32_t l, uint32_t r) const;
-  bool task_less(uint32_t l, uint32_t r) const;
-  double drf_share(const double *alloc, uint32_t mask) const;
+  bool job_less(uint32_t l, uint32_t r) const { return job_order_less(*pol_, *hs_, jshare, [this](uint32_t j) { return ready_num(j); }, l, r); }
+  bool task_less(uint32_t l, uint32_t r) const { return task_order_less(*pol_, *hs_, l, r); }
+  bool queue_less(uint32_t l, uint32_t r) const { return queue_order_less(*pol_, *hs_, qshare, l, r); }
   void fire_allocate(uint32_t t);
   void fire_deallocate(uint32_t t);
   void set_status(uint32_t t, int st);
@@ -142,8 +142,6 @@ class PreemptMachine {
   void commit();
   void discard();
   size_t evictable(uint32_t preemptor, const std::vector<uint32_t> &pre, std::vector<uint32_t> &victims, bool reclaim = false);
-  bool queue_less(uint32_t l, uint32_t r) const;
-  bool overused(uint32_t q) const;
   bool host_eval(uint32_t t, uint32_t n, long long &score) const;
   bool preempt_one(uint32_t preemptor, int mode);
   bool preempt_walk(uint32_t preemptor, int mode);
