@@ -1,18 +1,13 @@
 // kb_engine_int.hpp — what the translation units of the engine's host side share (round 6: kb_engine.cpp was one 2 400-line file): the engine
-// object, its device / pinned buffers, a round's context, the action's host state (ActionRun) and the helpers' declarations.
+// object, its device / pinned buffers, a round's context, the declaration of the action's host state (ActionRun) and of the helpers.
 //   kb_engine.cpp   create / destroy, buffers, timers, the closing reduction, the getters
 //   kb_load.cpp     kb_session_load (host session, uploads, water-fill launch), kb_session_reset
-//   kb_rounds.cpp   a round's three host steps, chaining and overlap, run_action (allocate / backfill), the round-granular API of the task-row split
+//   kb_rounds.cpp   a round's three host steps, chaining and overlap, ActionRun (the window planner, the feasibility probe, absorbing a round's
+//                   answer), run_action (allocate / backfill), the round-granular API of the task-row split
 //   kb_evict.cpp    the bridge between the evict machine (kb_preempt.cpp) and the device lists: kb_run_preempt / kb_run_reclaim
 //   kb_matrix.cpp   kb_eval_matrix / kb_argmax_rows / kb_bench_matrix (the materialised matrix)
 //
-//
-// Round structure: the host order machine speculates the reference's task order for a window of W
-// tasks (assuming each gets a node, which only ever fails when a whole feasibility class has died — and that is
-// monotone inside one action), the device evaluates the window's mask+score matrix against the round-start node
-// state (K1, once per distinct task shape), builds each shape's sorted candidate list (K3) and commits the window in the
-// reference's order, a run of same-shape rows at a time (K5).  A mis-speculation (no feasible node / Pipeline instead of Allocate) stops the commit kernel at that row;
-// the host rolls the order machine back to the round start, replays the confirmed prefix and re-plans.
+// Round structure: DESIGN.md §4 (kb_engine.cpp restates it at its top).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,7 +38,6 @@ using namespace kb;
   } while (0)
 
 namespace kbe {
-
 
 inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -225,9 +219,7 @@ struct kb_engine {
   double dirty_share = 0.0;   // share of rows won by a node the round had already changed (exponential average; a statistic)
   uint64_t rounds_run = 0, rounds_sel = 0;
   uint64_t sel_stat[4] = {0, 0, 0, 0};   // selection kernel: runs with every pick a clean first placement / committed by shots; shots cut short by a table's end; shots
-  uint32_t shape_cap = KB_K5_MAX_SHAPES;   // distinct shapes a window may hold (each keeps its candidate list in the commit kernel's LDS)
-  std::vector<uint32_t> plan_stamp;   // per row-shape id: stamp of the window being planned
-  uint32_t plan_epoch = 0;
+  uint32_t shape_cap = KB_K5_MAX_SHAPES;   // distinct shapes a window may hold (each keeps its candidate list in the commit kernel's LDS); ActionRun::admit_shape keeps to it
   const double *t_fit = nullptr;   // backfill's view of t_init (BestEffort rows: Resreq cpu / memory), == b_tinit when they agree
   bool idle_below_eps = false;
   DevBuf b_tfit;
@@ -278,7 +270,7 @@ struct kb_engine {
   int commit_kernel_of[2] = {0, 0};   // the commit kernel launched for the round in each staging half
   uint32_t win_cap = 0, mat_cap = 0;
   size_t keys_cap = 0;
-  Pinned<uint32_t> h_rows, h_slot, h_mrows;
+  Pinned<uint32_t> h_rows, h_slot, h_mrows;   // h_rows: kb_matrix.cpp's row range (a round's rows are its ActionRun's: Window)
   std::vector<uint32_t> h_decnode, h_deckind;
   Pinned<uint32_t> h_win;             // per-round upload  [rows | slots | mrows] at fixed offsets of KB_K5_MAX_WINDOW
   Pinned<unsigned long long> h_out;   // per-round download: KB_OUT_HDR header words (kb_device.h) + decision records
@@ -338,7 +330,7 @@ int guarded(kb_engine *e, const std::function<void()> &fn);
 
 // ---- rounds (kb_rounds.cpp)
 KbRound make_round(kb_engine *e, uint32_t n_rows, uint32_t n_mrows, uint32_t L, int fit_mode, bool backfill, uint32_t buf = 0);
-uint32_t assign_shapes(kb_engine *e, uint32_t n, const uint32_t *rows = nullptr);
+uint32_t assign_shapes(kb_engine *e, const uint32_t *rows, uint32_t n);
 // ---- one device round, in three host steps so the multi-GPU path can interleave its collectives ----
 struct RoundCtx {
   KbRound r{};
@@ -350,8 +342,8 @@ struct RoundCtx {
   unsigned long long seq = 0;    // the sequence number its commit kernel publishes
   bool overlapped = false;       // its candidate lists were built on the second stream and repaired (round_candidates_overlapped)
 };
-RoundCtx round_prepare(kb_engine *e, uint32_t n, int fit_mode, bool backfill, bool gather_in_matrix = false, const uint32_t *rows = nullptr,
-                       uint32_t buf = 0, uint32_t chain_expect = 0);
+RoundCtx round_prepare(kb_engine *e, const uint32_t *rows, uint32_t n, int fit_mode, bool backfill, bool gather_in_matrix = false, uint32_t buf = 0,
+                       uint32_t chain_expect = 0);
 void round_candidates(kb_engine *e, const RoundCtx &c, uint32_t m0, uint32_t m1, unsigned long long *keys);
 void ensure_overlap_buffers(kb_engine *e, uint32_t mrows, uint32_t stale_L);
 void round_candidates_overlapped(kb_engine *e, RoundCtx &c, uint32_t n_prev, unsigned long long *keys);
@@ -359,351 +351,78 @@ void round_commit(kb_engine *e, const RoundCtx &c, unsigned long long *keys, dou
 void round_collect(kb_engine *e, const RoundCtx &c, bool had_candidates, uint32_t &n_done, uint32_t &reason);
 void check_aggregates(kb_engine *e, const OrderMachine &om);
 
+// One planned window of an action and where it stands in run_action's pipeline
+struct Window {
+  std::vector<uint32_t> rows;   // task ids, eff_window entries (ActionRun::begin)
+  uint32_t n = 0;               // ... of which the planner filled this many
+  uint64_t pops = 0;            // what the order machine popped for them (tasks of dead shapes included)
+  bool planned = false;         // a speculated slot holds a window (n == 0: the order machine ran dry)
+  bool launched = false;        // its round is on the device: running (the current slot) or queued behind the running one (the next slot)
+  RoundCtx ctx;                 // ... that round
+  void set(uint32_t n_, uint64_t pops_) { n = n_; pops = pops_; planned = true; launched = false; }
+};
 
-// Host side of one action as a resumable object: plan() fills e->h_rows with the next window, absorb() digests the
-// device's answer (confirm, or roll back + replay on a mis-speculated round), finish() runs the gang/share reduction.
-// probes of more (shape, node) pairs than this run at every fourth break only (ActionRun::probe_launch); -DKB_PROBE_SPARSE_ABOVE=... for an A/B build
-#ifndef KB_PROBE_SPARSE_ABOVE
-#define KB_PROBE_SPARSE_ABOVE (8ull << 20)
-#endif
+// Host side of one action as a resumable object (bodies: kb_rounds.cpp): plan() fills the current window, absorb() digests the device's answer
+// (confirm, or roll back + replay on a mis-speculated round), finish() runs the gang/share reduction.  run_action drives it for
+// kb_run_allocate / kb_run_backfill, kb_round_* a round at a time through MgState.
 struct ActionRun {
   uint32_t action = 0;   // 0 allocate, 1 backfill
   bool bf_need_pred = false;
   std::vector<int> bf_podcnt;
   std::vector<unsigned long long> bf_ports, bf_ports_x;   // word 0 [NP]; the words behind it [port_xw][NP]
   OrderMachine om;
-  std::vector<uint8_t> dead;
+  std::vector<uint8_t> dead;   // per feasibility shape (mark_dead, the probe); backfill marks none
   std::vector<kb_decision> decs;
   std::vector<uint32_t> bf_list;
   size_t bf_pos = 0;
-  uint64_t popped = 0, spec_pops = 0, spec_pops_next = 0, spec_pops_next2 = 0;
-  std::vector<uint32_t> rows_next;   // the window speculated behind the one in flight
-  std::vector<uint32_t> rows_next2;  // ... and the one behind that: planned while the first two are on the device, launched when the first one's answer is in
+  uint64_t popped = 0;
+  Window cur, next, next2;   // the window the device works on (or is about to), the one speculated behind it, and the one behind that
+  std::vector<uint32_t> plan_stamp;   // per row-shape id: stamp of the window being planned
+  uint32_t plan_epoch = 0;
   std::vector<uint32_t> probe_list;  // feasibility shapes the probe looks at (the ones still alive)
-  uint32_t probe_calls = 0;
+  uint32_t probe_calls = 0, probe_S = 0;   // probe_S: rows of the probe in flight (0: none)
   double host_ms = 0, t_start = 0;
   bool active = false;
 
-  // A task shape with no feasible node stays infeasible for the rest of the action (idle only shrinks, releasing does not
-  // grow).  The same holds for every shape of the same static class whose compared InitResreq is >= in every dimension:
-  // LessEqual is monotone in its left operand, so that shape's feasible set is a subset of an empty set.  Marking them
-  // now saves the device round each would otherwise end.
-  void mark_dead(const HostSession &hs, uint32_t x) {
-    const int R = hs.R;
-    // inter-pod affinity: a shape that REQUIRES a matching pod in the node's domain gains nodes as pods are placed: never dead.
-    // Forbidding checks only shrink the feasible set (counts only grow inside allocate / backfill): dead stays dead, and a shape
-    // with the same checks and a larger request is dominated as usual.
-    if (!hs.feas_ip_require.empty() && hs.feas_ip_require[x]) return;
-    const double *ex = &hs.feas_eff[(size_t)x * R];
-    for (uint32_t y = 0; y < hs.n_feas_shapes; y++) {
-      if (dead[y] || hs.feas_cls[y] != hs.feas_cls[x] || hs.feas_conf[y] != hs.feas_conf[x]) continue;
-      if (hs.port_xw && std::memcmp(&hs.t_conf_x[(size_t)hs.feas_rep[y] * hs.port_xw], &hs.t_conf_x[(size_t)hs.feas_rep[x] * hs.port_xw], sizeof(uint64_t) * hs.port_xw) != 0) continue;
-      if (!hs.feas_ip.empty() && hs.feas_ip[y] != hs.feas_ip[x]) continue;
-      const double *ey = &hs.feas_eff[(size_t)y * R];
-      bool ge = true;
-      for (int d = 0; d < R && ge; d++) ge = ey[d] >= ex[d];
-      if (ge) dead[y] = 1;
-    }
-    dead[x] = 1;
-  }
-
-  void begin(kb_engine *e, uint32_t act) {
-    HostSession &hs = e->hs;
-    action = act;
-    decs.clear();
-    popped = spec_pops = 0;
-    host_ms = 0;
-    t_start = now_ms();
-    active = true;
-    ensure_window_buffers(e, e->eff_window);
-    if (action == 0) {
-      double t0 = now_ms();
-      om.init_allocate(&hs, &e->pol);
-      host_ms += now_ms() - t0;
-      dead.assign(hs.n_feas_shapes ? hs.n_feas_shapes : 1, 0);
-    } else {
-      // backfill.go:44-47: jobs ascending JobID, Pending tasks ascending UID with an empty InitResreq; the order does not
-      // depend on outcomes, so there is nothing to speculate
-      bf_list.clear();
-      bf_pos = 0;
-      for (uint32_t t : hs.init_empty_tasks)
-        if (hs.t_status[t] == KB_TASK_PENDING && hs.t_job[t] < hs.J) bf_list.push_back(t);
-      // Only a session with sub-epsilon BestEffort requests (or a node below -epsilon) can see AddTask refuse a node that passed
-      // the predicates; absorb() then needs to tell "no node passes the predicates" (the task stays Pending) from "one did"
-      // (outside the envelope).  Pod counts and used ports only grow during backfill, so the state as of now decides the former.
-      bf_need_pred = e->idle_below_eps;
-      if (hs.has_interpod)
-        for (uint32_t t : bf_list)
-          if (hs.t_res[t] != 0.0 || hs.t_res[(size_t)hs.T + t] != 0.0)
-            throw EngineError(KB_E_UNSUPPORTED, "BestEffort task with a sub-epsilon request in a session with inter-pod affinity");
-      for (uint32_t t : bf_list) bf_need_pred = bf_need_pred || hs.t_res[t] != 0.0 || hs.t_res[(size_t)hs.T + t] != 0.0;
-      if (bf_need_pred) {
-        const uint32_t NP = e->dev.NP;
-        bf_podcnt.resize(NP); bf_ports.assign(NP, 0);
-        HIP_OK(hipMemcpyAsync(bf_podcnt.data(), e->b_podcnt.p, sizeof(int) * NP, hipMemcpyDeviceToHost, e->stream));
-        if (e->dev.ports) HIP_OK(hipMemcpyAsync(bf_ports.data(), e->b_ports.p, sizeof(unsigned long long) * NP, hipMemcpyDeviceToHost, e->stream));
-        bf_ports_x.assign((size_t)e->dev.port_xw * NP, 0);
-        if (e->dev.port_xw) HIP_OK(hipMemcpyAsync(bf_ports_x.data(), e->b_ports_x.p, sizeof(unsigned long long) * bf_ports_x.size(), hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
-      }
-    }
-  }
-
-  // a window holds at most shape_cap distinct task shapes (one lane of the commit kernel's main wave each)
-  static void new_window(kb_engine *e) {
-    if (e->plan_stamp.size() != e->hs.n_row_shapes) { e->plan_stamp.assign(e->hs.n_row_shapes ? e->hs.n_row_shapes : 1, 0); e->plan_epoch = 0; }
-    e->plan_epoch++;
-  }
-  static bool admit_shape(kb_engine *e, uint32_t shape, uint32_t &nshapes) {
-    if (e->plan_stamp[shape] == e->plan_epoch) return true;
-    if (nshapes >= e->shape_cap) return false;
-    e->plan_stamp[shape] = e->plan_epoch;
-    nshapes++;
-    return true;
-  }
-
-  uint32_t plan(kb_engine *e) {
-    HostSession &hs = e->hs;
-    const uint32_t W = e->eff_window;
-    if (action == 1) {
-      uint32_t n = 0, nshapes = 0;
-      new_window(e);
-      while (n < W && bf_pos + n < bf_list.size() && !(n > 0 && !hs.t_ip_subject.empty() && hs.t_ip_subject[bf_list[bf_pos + n]]) &&
-             !(n > 0 && hs.wide(bf_list[bf_pos + n])) && admit_shape(e, hs.t_row_shape[bf_list[bf_pos + n]], nshapes)) {   // an inter-pod subject heads its window
-        e->h_rows[n] = bf_list[bf_pos + n];
-        n++;
-        if (hs.wide(e->h_rows[n - 1])) break;   // a pod whose host-port masks reach beyond word 0: a round of its own (kb_host.hpp)
-      }
-      return n;
-    }
-    double t0 = now_ms();
-    om.checkpoint();   // roll-back point for a mis-speculated round
-    uint32_t n = 0, t, nshapes = 0;
-    spec_pops = 0;
-    new_window(e);
-    while (n < W && om.next(t)) {
-      spec_pops++;
-      if (dead[hs.t_feas_shape[t]]) { om.report(Outcome::NoFeasibleNode); continue; }   // known: feasibility only shrinks inside one action
-      if (!admit_shape(e, hs.t_row_shape[t], nshapes) || (n > 0 && !hs.t_ip_subject.empty() && hs.t_ip_subject[t]) || (n > 0 && hs.wide(t))) {
-        om.rollback_last_pop(); spec_pops--; break;   // the task heads the next window (shape budget, an inter-pod subject: fresh matrix, or host-port masks beyond word 0)
-      }
-      e->h_rows[n++] = t;
-      om.report(Outcome::Allocated);
-      if (hs.wide(t)) break;   // ... and is that window's only row: the commit kernels keep to word 0 of the masks (kb_host.hpp: t_wide)
-    }
-    host_ms += now_ms() - t0;
-    if (n == 0) popped += spec_pops;
-    return n;
-  }
-
-  // While the device works on the window just launched, speculate the one after it (assuming the one in flight completes,
-  // which ~70 % do) behind a second roll-back point; promote() makes it the current window, a break rolls both back.
-  // `second`: the window behind the speculated one (rows_next2), behind a third roll-back point.  It is only PLANNED ahead — its matrix would be two
-  // rounds stale; run_action launches it when the round in flight has answered, and then has its rows ready: the order machine's ~30 us per
-  // window are no longer between a round's answer and the next launches (1M x 50k: the arg-max launch of the second stream was late for the
-  // commit launch by ~3 us per round, and by more on a slower host)
-  uint32_t plan_ahead(kb_engine *e, bool second = false) {
-    HostSession &hs = e->hs;
-    const uint32_t W = e->eff_window;
-    double t0 = now_ms();
-    om.push_checkpoint();
-    std::vector<uint32_t> &rows = second ? rows_next2 : rows_next;
-    uint64_t &pops = second ? spec_pops_next2 : spec_pops_next;
-    if (rows.size() < W) rows.resize(W);
-    uint32_t n = 0, t, nshapes = 0;
-    pops = 0;
-    new_window(e);
-    while (n < W && om.next(t)) {
-      pops++;
-      if (dead[hs.t_feas_shape[t]]) { om.report(Outcome::NoFeasibleNode); continue; }
-      if (!admit_shape(e, hs.t_row_shape[t], nshapes) || (n > 0 && !hs.t_ip_subject.empty() && hs.t_ip_subject[t]) || (n > 0 && hs.wide(t))) { om.rollback_last_pop(); pops--; break; }
-      rows[n++] = t;
-      om.report(Outcome::Allocated);
-      if (hs.wide(t)) break;
-    }
-    host_ms += now_ms() - t0;
-    return n;
-  }
-  // the window in flight is confirmed: the speculated one becomes the current one; with `have_second` the one planned behind it moves up
-  void promote(kb_engine *e, uint32_t n_next, bool have_second = false) {
-    om.pop_commit();
-    if (n_next) std::memcpy(e->h_rows.data(), rows_next.data(), sizeof(uint32_t) * n_next);
-    spec_pops = spec_pops_next;
-    if (n_next == 0) popped += spec_pops;
-    if (have_second) { rows_next.swap(rows_next2); spec_pops_next = spec_pops_next2; }
-  }
-
+  // starts the action: the order machine (allocate) or the BestEffort task list (backfill), no window planned, no shape dead
+  void begin(kb_engine *e, uint32_t act);
+  // feasibility shape x and every shape it dominates are dead for the rest of the action
+  void mark_dead(const HostSession &hs, uint32_t x);
+  // a window holds at most e->shape_cap distinct task shapes (one lane of the commit kernel's main wave each)
+  void new_window() { plan_epoch++; }
+  bool admit_shape(const kb_engine *e, uint32_t shape, uint32_t &nshapes);
+  // what the planner does with task t when the window being planned holds n rows of nshapes shapes: the admission rule, stated once
+  enum class Admit { Dead, Next, Join, Alone };
+  Admit admit(const kb_engine *e, uint32_t t, uint32_t n, uint32_t &nshapes);
+  // w := up to eff_window admitted tasks from the order machine, each reported as Allocated
+  void fill(kb_engine *e, Window &w);
+  // cur := the next window, behind a fresh roll-back point (allocate) or from bf_pos on (backfill); returns its row count, 0: the action is complete
+  uint32_t plan(kb_engine *e);
+  // next (`second`: next2) := the window behind the last one planned, behind a roll-back point of its own; returns its row count
+  uint32_t plan_ahead(kb_engine *e, bool second = false);
+  // the window in flight is confirmed: next becomes cur and next2 moves up; the slots rotate, no row is copied
+  void promote();
   // the plugin predicates of task t (predicates.go:127,181-190 and the static class table) against the pod counts / ports
   // backfill started from: a superset of the nodes that pass at any later point of the action
-  bool passed_predicates_at_start(kb_engine *e, uint32_t t) const {
-    const HostSession &hs = e->hs;
-    if (!e->pol.pred_enabled) return hs.N > 0;
-    const uint64_t conf = hs.t_conf.empty() ? 0 : hs.t_conf[t];
-    for (uint32_t n = 0; n < hs.N; n++) {
-      if (hs.n_maxpods[n] <= bf_podcnt[n]) continue;
-      if (!hs.compat.empty()) {
-        const uint32_t bit = hs.t_cls[t] * hs.n_nc + hs.n_cls[n];
-        if (!((hs.compat[bit >> 3] >> (bit & 7)) & 1)) continue;
-      }
-      if (bf_ports[n] & conf) continue;
-      bool clash = false;
-      for (uint32_t w = 0; w < hs.port_xw && !clash; w++) clash = (bf_ports_x[(size_t)w * e->dev.NP + n] & hs.t_conf_x[(size_t)t * hs.port_xw + w]) != 0;
-      if (clash) continue;
-      return true;
-    }
-    return false;
-  }
-
-  // At a speculation break the device is idle and the host is about to re-plan anyway: every feasibility shape that is still
-  // alive is evaluated against the current node state (one launch, feasibility only), and whatever has no node left is marked dead
-  // NOW instead of costing a break of its own when its next task comes up.  Exact: inside the allocate action a shape without a
-  // feasible node stays without one (the argument of mark_dead), so the reference's PredicateNodes will find none either when it
-  // pops such a task.  In two halves: probe_launch() right behind the answer of the round that broke (same stream: behind that round's
-  // commit kernel and the skipped round queued behind it; the node state it reads is final), probe_collect() in front of the re-plan —
-  // the host absorbs the answer (roll-back + replay, ~12 us) while the kernel runs.  The list is built from `dead` as the broken round was
-  // planned with; what absorb() marks meanwhile (the row that broke, the shapes it dominates) the probe finds dead again: not counted twice.
-  // No planned window is outstanding between the two halves, and absorb() of the allocate action launches nothing (sessions with host-port
-  // masks of several words, whose absorb() updates node words on the stream, probe behind it: run_action).
-  uint32_t probe_S = 0;   // rows of the probe in flight (0: none)
-  void probe_launch(kb_engine *e) {
-    HostSession &hs = e->hs;
-    probe_S = 0;
-    if (!e->probe_enabled || action != 0 || hs.has_interpod || hs.n_feas_shapes == 0 || !e->pol.pred_enabled) return;
-    // only the shapes that are still alive are looked at, and when that is a large matrix (many shapes x many nodes: a launch of
-    // a few hundred microseconds) only every fourth break pays for it; the deaths of the breaks in between are found then
-    probe_calls++;
-    probe_list.clear();
-    for (uint32_t f = 0; f < hs.n_feas_shapes; f++)
-      if (!dead[f]) probe_list.push_back(f);
-    const uint32_t S = (uint32_t)probe_list.size();
-    if (S == 0) return;
-    if ((uint64_t)S * hs.N > KB_PROBE_SPARSE_ABOVE && (probe_calls & 3u) != 1u) return;
-    for (uint32_t i = 0; i < S; i++) { e->h_probe_rows[i] = hs.feas_rep[probe_list[i]]; e->h_probe_alive[i] = 0u; }
-    kb_launch_probe(e->dev, e->d_probe_rows, S, e->d_probe_alive, e->stream);
-    probe_S = S;
-  }
-  void probe_collect(kb_engine *e) {
-    if (probe_S == 0) return;
-    const uint32_t S = probe_S;
-    probe_S = 0;
-    HIP_OK(hipStreamSynchronize(e->stream));
-    e->probes++;
-    for (uint32_t i = 0; i < S; i++)   // no dominance scan needed: the probe looked at every live shape itself
-      if (e->h_probe_alive[i] == 0 && !dead[probe_list[i]]) { dead[probe_list[i]] = 1; e->probe_deaths++; }
-  }
-  void probe_abandon(kb_engine *e) {   // an exception between the halves: the kernel must not outlive the call (it writes into h_probe_alive)
-    if (probe_S) { (void)hipStreamSynchronize(e->stream); probe_S = 0; }
-  }
+  bool passed_predicates_at_start(kb_engine *e, uint32_t t) const;
+  // the feasibility probe: every shape still alive without a node in the current state is marked dead.  In two halves around the host's work on
+  // a break's answer; probe_abandon() when that work throws between them (the kernel must not outlive the call: it writes into h_probe_alive)
+  void probe_launch(kb_engine *e);
+  void probe_collect(kb_engine *e);
+  void probe_abandon(kb_engine *e) { if (probe_S) { (void)hipStreamSynchronize(e->stream); probe_S = 0; } }
   void probe_dead_shapes(kb_engine *e) { probe_launch(e); probe_collect(e); }
-
-  // host-port masks of several words: the placed pod's words behind the first join the node's (both ssn.Allocate and ssn.Pipeline end in
-  // NodeInfo.AddTask; the kernels advanced word 0).  On the action's stream, in front of whatever the next round launches.
-  void absorb(kb_engine *e, uint32_t n, uint32_t n_done, uint32_t reason) {
-    const size_t first = decs.size();
-    absorb_round(e, n, n_done, reason);
-    if (e->dev.port_xw)
-      for (size_t i = first; i < decs.size(); i++)
-        if (e->hs.wide(decs[i].task) && decs[i].node != KB_NONE) kb_launch_or_ports_x(e->dev, decs[i].task, decs[i].node, e->stream);
-  }
-  void absorb_round(kb_engine *e, uint32_t n, uint32_t n_done, uint32_t reason) {
-    HostSession &hs = e->hs;
-    const uint32_t round = (uint32_t)(e->round_no - 1);
-    if (action == 1) {
-      if (reason != KB_REASON_DONE || n_done != n) throw EngineError(KB_E_INTERNAL, "backfill round ended early");
-      for (uint32_t i = 0; i < n; i++) {
-        const uint32_t t = e->h_rows[i];
-        if (e->h_decnode[i] != KB_NONE) { decs.push_back(kb_decision{t, e->h_decnode[i], 0u, round}); continue; }
-        // No node took the task.  With a zero request that means no node passes the predicates and the task stays Pending
-        // (unless a node's Idle sat at or below -epsilon in the snapshot).  With a non-zero sub-epsilon request a node may have passed
-        // the predicates and failed AddTask: ssn.Allocate has then flipped the task to Allocated without a node
-        // (session.go:243 before :255), and what a later dispatch of that job does with it depends on Go's map order.
-        if ((hs.t_res[t] != 0.0 || hs.t_res[(size_t)hs.T + t] != 0.0 || e->idle_below_eps) && passed_predicates_at_start(e, t))
-          throw EngineError(KB_E_UNSUPPORTED, "BestEffort task with a sub-epsilon request found no node (the reference may leave it Allocated without one)");
-      }
-      bf_pos += n;
-      return;
-    }
-    double t0 = now_ms();
-    if (reason == KB_REASON_DONE) {
-      popped += spec_pops;
-      for (uint32_t i = 0; i < n; i++) decs.push_back(kb_decision{e->h_rows[i], e->h_decnode[i], e->h_deckind[i], round});
-    } else {
-      // replay the confirmed prefix on the checkpoint, then feed the true outcome of the row that broke the speculation
-      e->stats.spec_breaks += 1;
-      om.rollback();
-      uint32_t i = 0, t;
-      for (;;) {
-        if (!om.next(t)) throw EngineError(KB_E_INTERNAL, "order replay ran out of tasks");
-        popped++;
-        if (dead[hs.t_feas_shape[t]]) { om.report(Outcome::NoFeasibleNode); continue; }
-        if (t != e->h_rows[i]) throw EngineError(KB_E_INTERNAL, "order replay diverged from the speculated sequence");
-        if (reason == KB_REASON_NO_FEASIBLE && i == n_done) {
-          mark_dead(hs, hs.t_feas_shape[t]);
-          om.report(Outcome::NoFeasibleNode);
-          break;
-        }
-        if (reason == KB_REASON_SKIPPED && i == n_done) {
-          // only an overlapped round whose candidate lists never arrived skips itself behind a predecessor that completed (k_repair's
-          // bounded wait): nothing was decided; the task heads the next window, which goes the plain way — and so does every round of this
-          // engine from now on (overlap_faults is never cleared: a launch that got lost on the second stream is not expected to heal)
-          e->overlap_faults += 1;
-          om.rollback_last_pop();
-          popped--;
-          break;
-        }
-        if (reason == KB_REASON_RENORM && i == n_done) {
-          // the device stopped in front of this task (its score must be normalised over a fresh feasible set): nothing was
-          // decided for it; undo the pop so that it heads the next window
-          om.rollback_last_pop();
-          popped--;
-          break;
-        }
-        decs.push_back(kb_decision{t, e->h_decnode[i], e->h_deckind[i], round});
-        om.report(e->h_deckind[i] ? Outcome::Pipelined : Outcome::Allocated);
-        i++;
-        if (reason == KB_REASON_PIPELINED && i == n_done) break;
-      }
-    }
-    host_ms += now_ms() - t0;
-  }
-
-  void finish(kb_engine *e) {
-    HostSession &hs = e->hs;
-    // every ssn.Allocate / ssn.Pipeline fires proportion's AllocateFunc -> updateShare for the task's queue (proportion.go:212-223)
-    for (const kb_decision &dc : decs) {
-      const uint32_t q = hs.job_queue[hs.t_job[dc.task]];
-      if (q < hs.Q) hs.queue_share_live[q] = 1;
-    }
-    // an action that decided nothing left the task table as the last reduction saw it (every call that changes it ends with one):
-    // the host mirrors are current, nothing to recount (a cycle's backfill usually finds no BestEffort task at all)
-    const double t_fin0 = now_ms();
-    if (!decs.empty()) run_finalize(e);
-    e->tl_finish += now_ms() - t_fin0;
-    if (action == 0) {
-      check_aggregates(e, om);
-      e->stats.tasks_popped += popped;
-      e->stats.evals += popped * (uint64_t)hs.N;   // PredicateNodes visits every node for every popped task (allocate.go:143)
-    } else {
-      e->stats.tasks_popped += bf_list.size();
-      // the reference stops at the first node that passes: count the nodes it actually visits
-      uint64_t ev = 0;
-      std::vector<uint8_t> placed(hs.T, 0);
-      for (auto &dcs : decs) { placed[dcs.task] = 1; ev += (uint64_t)dcs.node + 1; }
-      for (uint32_t t : bf_list) if (!placed[t]) ev += hs.N;
-      e->stats.evals += ev;
-    }
-    e->stats.decisions += decs.size();
-    e->stats.host_order_ms += host_ms;
-    e->stats.total_ms += now_ms() - t_start;
-    active = false;
-  }
+  // the answer (n_done rows, reason) to cur's round: its decisions join decs; a break rolls the order machine back to the round's start, replays
+  // the confirmed prefix and feeds the true outcome of the row that broke.  absorb() = absorb_round() + the placed pods' host-port words behind the first
+  void absorb(kb_engine *e, uint32_t n_done, uint32_t reason);
+  void absorb_round(kb_engine *e, uint32_t n_done, uint32_t reason);
+  // the closing reduction (when anything was decided), the aggregate cross-check, the action's share of kb_stats
+  void finish(kb_engine *e);
 };
 
 }  // namespace kbe
 
 struct MgState {
-  ActionRun run;
-  RoundCtx ctx;
+  ActionRun run;   // run.cur.ctx is the round between kb_round_begin and kb_round_apply
   bool in_round = false, committed = false, had_candidates = false;
   uint32_t n_done = 0, reason = 0;
   std::vector<kb_decision> last_decs;

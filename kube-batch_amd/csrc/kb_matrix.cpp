@@ -23,7 +23,7 @@ static ChunkPlan matrix_plan(kb_engine *e, uint32_t t0, uint32_t n, uint32_t fit
   ensure_matrix_buffers(e, n, k ? k : 1);
   for (uint32_t i = 0; i < n; i++) e->h_rows[i] = t0 + i;
   if (e->h_mrows.size() < n) e->h_mrows.resize(n);
-  p.ns = assign_shapes(e, n);
+  p.ns = assign_shapes(e, e->h_rows.data(), n);
   // Expansion streams every task row out of its shape's row.  The rows are expanded in SHAPE order (`order`), so a shape
   // row is read from HBM once and copied to all its task rows out of the L2 however many shapes there are; what the per-shape pass
   // cannot avoid is evaluating and storing the shape rows themselves.  When (nearly) every job has its own request that is a second

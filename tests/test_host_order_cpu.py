@@ -150,7 +150,7 @@ def _feas_shapes(snap, p):
 
 
 def _drive(L, cfg, snap, window, ahead, renorm_prob, rng):
-    """ActionRun::plan / plan_ahead / promote / absorb and run_action's loop (kb_engine.cpp), with pyref as the device."""
+    """ActionRun::plan / plan_ahead / promote / absorb and run_action's loop (kb_rounds.cpp), with pyref as the device."""
     p = pyref.Session(cases._tiers(cfg), snap)
     m = Machine(L, cfg, snap, p)
     shape, eff = _feas_shapes(snap, p)
