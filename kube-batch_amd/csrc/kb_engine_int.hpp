@@ -1,7 +1,7 @@
 // kb_engine_int.hpp — what the translation units of the engine's host side share (round 6: kb_engine.cpp was one 2 400-line file): the engine
 // object, its device / pinned buffers, a round's context, the declaration of the action's host state (ActionRun) and of the helpers.
 //   kb_engine.cpp   create / destroy, buffers, timers, the closing reduction, the getters
-//   kb_load.cpp     kb_session_load (host session, uploads, water-fill launch), kb_session_reset
+//   kb_load.cpp     kb_session_load (host session, uploads, water-fill launch) as named steps, kb_session_reset, the one list of the state it restores
 //   kb_rounds.cpp   a round's three host steps, chaining and overlap, ActionRun (the window planner, the feasibility probe, absorbing a round's
 //                   answer), run_action (allocate / backfill), the round-granular API of the task-row split
 //   kb_evict.cpp    the bridge between the evict machine (kb_preempt.cpp) and the device lists: kb_run_preempt / kb_run_reclaim
@@ -20,6 +20,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -67,6 +68,10 @@ struct DevBuf {
     HIP_OK(hipMalloc(&p, cap));
   }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+  void copy_of(const DevBuf &src, hipStream_t s) {   // this := src, device to device on s, nothing waited for
+    alloc(src.bytes);
+    HIP_OK(hipMemcpyAsync(p, src.p, src.bytes, hipMemcpyDeviceToDevice, s));
+  }
 };
 
 // grow-only pinned host array: the per-round staging buffers (window rows in, decision records out) are copied with
@@ -127,48 +132,56 @@ struct PinnedArena {
 };
 constexpr size_t kStageMaxBytes = (size_t)8 << 20;
 
+// What an upload hands back: the device copy, typed as its source, so that a KbDev view is bound on the line of its upload.  It converts to a
+// pointer to any element type of the same size, signedness and kind (the ABI's int64_t / uint64_t arrays are KbDev's long long / unsigned long long).
+template <typename T> struct DevPtr {
+  T *p;
+  template <typename U, typename = std::enable_if_t<sizeof(U) == sizeof(T) && std::is_signed<U>::value == std::is_signed<T>::value &&
+                                                    std::is_floating_point<U>::value == std::is_floating_point<T>::value>>
+  operator U *() const { return reinterpret_cast<U *>(p); }
+};
+
 struct Uploader {
   PinnedArena &arena;
   hipStream_t s;
   Uploader(PinnedArena &a, hipStream_t st) : arena(a), s(st) {}
-  // b := n elements the caller writes through the returned pointer BEFORE the next take / copy (the copy is queued by commit())
+  // b := n elements the caller writes through the returned pointer BEFORE the next take / copy (the copy is queued by commit(), which takes that pointer)
   template <typename T> T *stage(DevBuf &b, size_t n) {
     b.alloc(n * sizeof(T));
     pending_dst = b.p; pending_bytes = n * sizeof(T);
-    pending_src = arena.take(pending_bytes ? pending_bytes : 16);
-    return reinterpret_cast<T *>(pending_src);
+    return reinterpret_cast<T *>(arena.take(pending_bytes ? pending_bytes : 16));
   }
-  void commit() {
-    if (pending_bytes) HIP_OK(hipMemcpyAsync(pending_dst, pending_src, pending_bytes, hipMemcpyHostToDevice, s));
+  template <typename T> DevPtr<T> commit(T *staged) {
+    if (pending_bytes) HIP_OK(hipMemcpyAsync(pending_dst, staged, pending_bytes, hipMemcpyHostToDevice, s));
     pending_bytes = 0;
+    return {reinterpret_cast<T *>(pending_dst)};
   }
   // any source: copied into the area first (the source may die before the load's synchronisation: block-scoped temporaries)
-  template <typename T> void copy(DevBuf &b, const T *src, size_t n) {
+  template <typename T> DevPtr<T> copy(DevBuf &b, const T *src, size_t n) {
     T *p = stage<T>(b, n);
     if (n) std::memcpy(p, src, n * sizeof(T));
-    commit();
+    return commit(p);
   }
   // a source that outlives the load's synchronisation (the caller's snapshot, the host session's vectors): from 8 MiB on straight from where it
   // lies — the runtime pins it for the transfer; one pin per call is cheaper than an extra pass over a million-task vector
-  template <typename T> void copy_persistent(DevBuf &b, const T *src, size_t n) {
-    if (n * sizeof(T) >= kStageMaxBytes) {
-      b.alloc(n * sizeof(T));
-      HIP_OK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-      return;
-    }
-    copy(b, src, n);
+  template <typename T> DevPtr<T> copy_persistent(DevBuf &b, const T *src, size_t n) {
+    if (n * sizeof(T) < kStageMaxBytes) return copy(b, src, n);
+    b.alloc(n * sizeof(T));
+    HIP_OK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return {b.as<T>()};
   }
-  // rows of a [rows][n] host matrix into a padded [rows][np] device matrix (pad value `fill`)
-  template <typename T> void padded(DevBuf &b, const T *src, size_t rows, size_t n, size_t np, T fill = T(0)) {
-    T *p = stage<T>(b, rows * np);
+  // rows of a [rows][n] host matrix into a padded [max(rows, 1)][np] device matrix (the pad, and the one row of a matrix without rows: `fill`)
+  template <typename T> DevPtr<T> padded(DevBuf &b, const T *src, size_t rows, size_t n, size_t np, T fill = T(0)) {
+    T *p = stage<T>(b, std::max<size_t>(rows, 1) * np);
+    if (!rows) std::fill(p, p + np, fill);
     for (size_t r = 0; r < rows; r++) {
       if (n) std::memcpy(p + r * np, src + r * n, n * sizeof(T));
       std::fill(p + r * np + n, p + (r + 1) * np, fill);
     }
-    commit();
+    return commit(p);
   }
  private:
-  void *pending_dst = nullptr, *pending_src = nullptr;
+  void *pending_dst = nullptr;
   size_t pending_bytes = 0;
 };
 
@@ -224,12 +237,14 @@ struct kb_engine {
   bool idle_below_eps = false;
   DevBuf b_tfit;
   DevBuf b_tinit, b_tres, b_tnzc, b_tnzm, b_tcls, b_tactive, b_tresmask, b_tjob, b_tstatus, b_tnode, b_tbind, b_tcounted, b_jallocated, b_compat, b_crows, b_aff, b_affcls;
-  DevBuf p_idle, p_rel, p_nzc, p_nzm, p_podcnt, p_tstatus, p_tnode, p_tcounted, p_ports, p_nmask;   // pristine copies for kb_session_reset
-  // inter-pod (anti)affinity tables (kb_interpod) and the pristine copies of their live parts
+  // pristine copies for kb_session_reset, one per entry of kb_load.cpp's for_each_live: THE list of the buffers an action changes on the device
+  // (the load's snapshot and the reset's restore both walk it; a new live buffer is one line there and nothing here)
+  std::unique_ptr<DevBuf[]> p_live;
+  // inter-pod (anti)affinity tables (kb_interpod)
   DevBuf b_ip_cdom, b_ip_ccnt, b_ip_ctot, b_ip_tinc, b_ip_tforbid, b_ip_treq, b_ip_tself, b_ip_tsubj, b_ip_tchk, b_ip_pdom, b_ip_pbound, b_ip_punb, b_ip_tcinc,
-      b_ip_tsig, b_ip_sigw, b_ip_z, b_ip_scnt, b_ip_shist, p_ip_ccnt, p_ip_ctot, p_ip_punb, p_ip_z;
+      b_ip_tsig, b_ip_sigw, b_ip_z, b_ip_scnt, b_ip_shist;
   DevBuf b_ports, b_twant, b_tconf;   // host ports (only when the snapshot carries any)
-  DevBuf b_ports_x, b_twant_x, b_tconf_x, p_ports_x;   // their words behind the first (kb_snapshot.port_words > 1 and some pod reaches there), pristine copy
+  DevBuf b_ports_x, b_twant_x, b_tconf_x;   // their words behind the first (kb_snapshot.port_words > 1 and some pod reaches there)
   DevBuf b_jbegin, b_jmin, b_jqueue, b_total, b_deserved, b_desmask, b_jalloc, b_jshare, b_qalloc, b_qshare, b_jready;
   uint32_t total_mask = 0;
   // round buffers
@@ -421,17 +436,25 @@ struct ActionRun {
 
 }  // namespace kbe
 
+// The node state at the start of a round of the task-row split (kb_round_*): the reduced deltas are applied to it and checked against it
+struct NodeStart {
+  DevBuf idle, rel, nzc, nzm, podcnt;
+  void take(kb_engine *e) {   // five device-to-device copies of the live arrays on e->stream
+    idle.copy_of(e->b_idle, e->stream); rel.copy_of(e->b_rel, e->stream); nzc.copy_of(e->b_nzc, e->stream); nzm.copy_of(e->b_nzm, e->stream); podcnt.copy_of(e->b_podcnt, e->stream);
+  }
+  KbNodeCopy view() const { return KbNodeCopy{idle.as<double>(), rel.as<double>(), nzc.as<long long>(), nzm.as<long long>(), podcnt.as<int>()}; }
+  void swap(NodeStart &o) { idle.swap(o.idle); rel.swap(o.rel); nzc.swap(o.nzc); nzm.swap(o.nzm); podcnt.swap(o.podcnt); }
+};
+
 struct MgState {
   ActionRun run;   // run.cur.ctx is the round between kb_round_begin and kb_round_apply
   bool in_round = false, committed = false, had_candidates = false;
   uint32_t n_done = 0, reason = 0;
   std::vector<kb_decision> last_decs;
-  DevBuf s_idle, s_rel, s_nzc, s_nzm, s_podcnt;   // node state at round start
-  // the deferred cross-check (kb_round_check): the state at the start of the round BEFORE the current one, a device counter of differing
-  // values that lives for the action, the rounds begun in it
-  DevBuf q_idle, q_rel, q_nzc, q_nzm, q_podcnt, chk_counter;
+  // node state at the start of the round and of the one BEFORE it: the deferred cross-check (kb_round_check) compares that round's reduced deltas
+  // against the two, one round late; a device counter of differing values that lives for the action, the rounds begun in it
+  NodeStart cur, prev;
+  DevBuf chk_counter;
   uint32_t rounds_begun = 0;
   bool chk_valid = false;   // chk_counter belongs to an action begun since the last load / reset
-  KbNodeCopy cur() const { return KbNodeCopy{s_idle.as<double>(), s_rel.as<double>(), s_nzc.as<long long>(), s_nzm.as<long long>(), s_podcnt.as<int>()}; }
-  KbNodeCopy prev() const { return KbNodeCopy{q_idle.as<double>(), q_rel.as<double>(), q_nzc.as<long long>(), q_nzm.as<long long>(), q_podcnt.as<int>()}; }
 };

@@ -803,13 +803,9 @@ int kb_round_begin(kb_engine *e, uint32_t action, uint32_t *n_rows, uint32_t *n_
     m.in_round = true;
     // round-start copy of the node state: the reduced deltas are applied to it.  The copy of the round before stays (kb_round_check compares
     // that round's reduced deltas against the two of them, one round late)
-    m.q_idle.swap(m.s_idle); m.q_rel.swap(m.s_rel); m.q_nzc.swap(m.s_nzc); m.q_nzm.swap(m.s_nzm); m.q_podcnt.swap(m.s_podcnt);
+    m.prev.swap(m.cur);
     m.rounds_begun += 1;
-    auto snap = [&](DevBuf &dst, const DevBuf &src) {
-      if (dst.bytes != src.bytes) dst.alloc(src.bytes);
-      HIP_OK(hipMemcpyAsync(dst.p, src.p, src.bytes, hipMemcpyDeviceToDevice, e->stream));
-    };
-    snap(m.s_idle, e->b_idle); snap(m.s_rel, e->b_rel); snap(m.s_nzc, e->b_nzc); snap(m.s_nzm, e->b_nzm); snap(m.s_podcnt, e->b_podcnt);
+    m.cur.take(e);
     if (n_mrows) *n_mrows = m.run.cur.ctx.ns;
     if (list_len) *list_len = m.run.cur.ctx.L;
   });
@@ -854,8 +850,9 @@ int kb_round_apply(kb_engine *e, uint64_t dev_delta_ptr, uint32_t *done) {
     MgState &m = *e->mg;
     if (dev_delta_ptr) {
       // node state for the next round = round-start state + all-reduced deltas; it must equal this replica's own commit
-      uint32_t mism = kb_apply_deltas(e->dev, m.s_idle.as<double>(), m.s_rel.as<double>(), m.s_nzc.as<long long>(), m.s_nzm.as<long long>(),
-                                      m.s_podcnt.as<int>(), reinterpret_cast<const double *>(dev_delta_ptr), e->b_out.as<uint32_t>() + 8, e->stream);   // word [4] of the output block
+      const KbNodeCopy s0 = m.cur.view();
+      const double *delta = reinterpret_cast<const double *>(dev_delta_ptr);
+      uint32_t mism = kb_apply_deltas(e->dev, s0.idle, s0.rel, s0.nzc, s0.nzm, s0.podcnt, delta, e->b_out.as<uint32_t>() + 8, e->stream);   // word [4] of the output block
       if (mism) throw EngineError(KB_E_INTERNAL, "replicas diverged: reduced per-node deltas differ from the local commit at " + std::to_string(mism) + " values");
     }
     m.run.absorb(e, m.n_done, m.reason);
@@ -877,10 +874,10 @@ int kb_round_check(kb_engine *e, uint64_t dev_delta_ptr, uint32_t against_live) 
     const KbDev &d = e->dev;
     if (against_live) {   // the action's last round: its start copy + deltas == the live state (the kb_round_begin that ended the action took no copy)
       if (m.in_round || m.rounds_begun < 1) throw EngineError(KB_E_STATE, "kb_round_check(against_live): behind the kb_round_begin that ended the action");
-      kb_check_deltas(d, m.cur(), KbNodeCopy{d.idle, d.rel, d.nzc, d.nzm, d.podcnt}, delta, m.chk_counter.as<uint32_t>(), e->stream);
+      kb_check_deltas(d, m.cur.view(), KbNodeCopy{d.idle, d.rel, d.nzc, d.nzm, d.podcnt}, delta, m.chk_counter.as<uint32_t>(), e->stream);
     } else {              // round k's deltas, round k + 1 begun: the two start copies
       if (!m.in_round || m.rounds_begun < 2) throw EngineError(KB_E_STATE, "kb_round_check: behind the kb_round_begin of the NEXT round");
-      kb_check_deltas(d, m.prev(), m.cur(), delta, m.chk_counter.as<uint32_t>(), e->stream);
+      kb_check_deltas(d, m.prev.view(), m.cur.view(), delta, m.chk_counter.as<uint32_t>(), e->stream);
     }
   });
 }

@@ -795,3 +795,67 @@ def test_runs_of_identical_rows_committed_by_one_selection(emulated_engine, mode
         assert "wrong 0 of 4" in r.stdout, r.stdout
     else:
         assert "wrong 0 of 4" not in r.stdout, r.stdout
+
+
+# ---- kb_session_load refuses a snapshot with several defects by the FIRST of them in the load's own order ------------------------------------
+def _hand_snapshot(n_nodes=2, **over):
+    """2 nodes (or n_nodes), 3 Pending tasks in one job of one queue, 2 task classes, 2 node classes; valid until `over` plants its defects"""
+    N, T, Gi = n_nodes, 3, float(1 << 30)
+    f = dict(
+        n_res=2, n_nodes=N, n_tasks=T, n_jobs=1, n_queues=1, n_task_classes=2, n_node_classes=2,
+        node_idle=np.array([[8000.0] * N, [16 * Gi] * N]), node_releasing=np.zeros((2, N)), node_allocatable=np.array([[8000.0] * N, [16 * Gi] * N]),
+        node_scalar_mask=np.zeros(N, np.uint32), node_alloc_cpu=np.full(N, 8000, np.int64), node_alloc_mem=np.full(N, 16 << 30, np.int64),
+        node_nz_cpu=np.zeros(N, np.int64), node_nz_mem=np.zeros(N, np.int64), node_max_pods=np.full(N, 110, np.int32),
+        node_pod_cnt=np.zeros(N, np.int32), node_class=np.arange(N, dtype=np.uint32) % 2,
+        task_resreq=np.array([[1000.0] * T, [Gi] * T]), task_init_resreq=np.array([[1000.0] * T, [Gi] * T]), task_scalar_mask=np.zeros(T, np.uint32),
+        task_nz_cpu=np.full(T, 1000, np.int64), task_nz_mem=np.full(T, 1 << 30, np.int64), task_job=np.zeros(T, np.uint32),
+        task_class=np.array([0, 1, 0], np.uint32), task_priority=np.zeros(T, np.int32), task_creation=np.arange(T, dtype=np.int64),
+        task_status=np.full(T, abi.TASK_PENDING, np.uint8), task_node=np.full(T, 0xFFFFFFFF, np.uint32),
+        job_task_begin=np.array([0, T], np.uint32), job_queue=np.zeros(1, np.uint32), job_min_available=np.ones(1, np.int32),
+        job_priority=np.zeros(1, np.int32), job_creation=np.zeros(1, np.int64), queue_weight=np.ones(1, np.int32), queue_creation=np.zeros(1, np.int64))
+    f.update(over)
+    return kbm.snapshot.SessionSnapshot(**f)
+
+
+_ALL_COMPATIBLE = np.array([0x0F], np.uint8)                       # 2 x 2 classes, every pair compatible
+_NO_AFFINITY = np.zeros(4, np.int32)
+_PORTS_NOT_SUBSET = dict(task_port_want=np.array([0, 3, 0], np.uint64), task_port_conflict=np.array([0, 1, 0], np.uint64))
+_MULTI_DEFECT = {
+    # name: (nodeorder weights (least, most, nodeaffinity, balanced), node count, the planted defects, the refusal of the parent build: code, text)
+    "task_class+ports/compat": ((1, 0, 1, 1), 2, dict(task_class=np.array([0, 2, 0], np.uint32), class_compat=_ALL_COMPATIBLE, **_PORTS_NOT_SUBSET),
+                                ("KB_E_INVALID", "task class out of range")),
+    "task_class+ports/affinity": ((1, 0, 1, 1), 2, dict(task_class=np.array([0, 2, 0], np.uint32), class_affinity=_NO_AFFINITY, **_PORTS_NOT_SUBSET),
+                                  ("KB_E_INVALID", "a pod's host ports must conflict with themselves (want is not a subset of conflict)")),
+    "node_class+affinity_count": ((1, 0, 1, 1), 2, dict(node_class=np.array([0, 2], np.uint32), class_affinity=np.array([0, 100001, 0, 0], np.int32)),
+                                  ("KB_E_INVALID", "node class out of range")),
+    "node_class+affinity_count/compat": ((1, 0, 1, 1), 2, dict(node_class=np.array([0, 2], np.uint32), class_compat=_ALL_COMPATIBLE,
+                                                              class_affinity=np.array([0, -1, 0, 0], np.int32)),
+                                         ("KB_E_INVALID", "node class out of range")),
+    "affinity_count+ports": ((1, 0, 1, 1), 2, dict(class_affinity=np.array([0, 100001, 0, 0], np.int32), **_PORTS_NOT_SUBSET),
+                             ("KB_E_INVALID", "a pod's host ports must conflict with themselves (want is not a subset of conflict)")),
+    # 10 * (3000 + 3000 + 554) = 65540 > 65535: kb_engine_create's policy compiler holds the same bound as the load's affinity step and answers first,
+    # so the load's own "nodeorder weights exceed the 16-bit score range" cannot be reached through the C ABI
+    "weights+compat": ((3000, 0, 3000, 554), 2, dict(class_compat=_ALL_COMPATIBLE, class_affinity=np.array([0, 5, 0, 0], np.int32)),
+                       ("KB_E_UNSUPPORTED", "nodeorder weights must be >= 0 with 10*(least+most+balanced+nodeaffinity) <= 65535 (u16 score)")),
+    # 65 537 nodes pad to 67 584: 17 node bits, and (10 * 3277 + 2) << 17 > 2^32 (no weight set the policy compiler accepts overflows 16 node bits)
+    "keys+task_class": ((3277, 0, 0, 0), 65537, dict(task_class=np.array([0, 2, 0], np.uint32), class_compat=_ALL_COMPATIBLE),
+                        ("KB_E_UNSUPPORTED", "score range x node count exceeds the commit kernel's 32-bit keys")),
+    "keys+node_class/affinity": ((0, 3000, 277, 0), 65537, dict(node_class=np.full(65537, 2, np.uint32), class_affinity=np.array([0, 5, 0, 0], np.int32)),
+                                 ("KB_E_UNSUPPORTED", "score range x node count exceeds the commit kernel's 32-bit keys")),
+}
+
+
+def test_load_refusal_order(emulated_engine):
+    """kb_session_load validates as it uploads, so WHICH refusal a snapshot with two defects gets is the order of the load's steps: key range, then per
+    table (compat, host ports, affinity) the class ranges in front of the table's own checks.  Code and kb_last_error text, recorded from the build in
+    front of the split of the load into named steps; no other test notices a step that moved.  (One test over all cases: each takes milliseconds.)"""
+    import test_pyref_vs_oracle as cases
+    for name, ((wl, wm, wa, wb), n_nodes, defects, want) in sorted(_MULTI_DEFECT.items()):
+        cfg = kbm.conf.load_scheduler_conf(cases.CONF_TMPL.format(wl=wl, wm=wm, wa=wa, wb=wb))
+        with pytest.raises(engine.EngineError) as err:
+            e = engine.Engine(cfg)
+            try:
+                e.load(_hand_snapshot(n_nodes, **defects))
+            finally:
+                e.close()
+        assert (err.value.code, str(err.value)) == (getattr(abi, want[0]), f"{want[0]}: {want[1]}"), name
