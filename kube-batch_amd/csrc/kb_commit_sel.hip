@@ -30,6 +30,7 @@
 //      wave 0       when both are there: the selection (or the serial loop), decision records, cursors, dirty slots; publish seq_done = k + 1.
 //    A run's critical path is one evaluation (dirty slots) and its selection.  The words only grow; every wait is bounded (a wave that
 //    waits too long raises `err`, everybody leaves, the round reports KB_REASON_INTERNAL instead of hanging).
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -56,6 +57,10 @@ __device__ __forceinline__ bool k9s_wait(K9Sync &Y, const uint32_t *p, uint32_t 
     if (nap == 0u) { } else if (nap == 1u) __builtin_amdgcn_s_sleep(1); else if (nap <= 4u) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(16);   // (s_sleep takes an immediate)
   }
 }
+
+#ifdef KB_K9_TRACE
+__device__ unsigned long long k9s_wait_split[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS];   // kb_k9.hpp: K9_WSPLIT_*, summed over every round since the last print
+#endif
 
 __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs ka) {
   KbCommitArgs a = ka.hot;
@@ -107,6 +112,9 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
   //      the longest run.  W <= KB_K5_MAX_ROWS = 256: eight mask words.
   if (tid < 8) { X.brk[tid] = 0u; X.stm[tid] = 0u; }
   if (tid < 4) { X.stat[tid] = 0u; X.tr[tid] = 0u; }
+#ifdef KB_K9_TRACE
+  if (tid < K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS) X.wsplit[tid] = 0u;
+#endif
   if (tid < sizeof(K9Sync) / 4) reinterpret_cast<uint32_t *>(&Y)[tid] = 0u;   // every sequence word starts at 0; nd_at[0] = 0: run 0 finds no dirty slot
   __syncthreads();
   if (tid < W) {
@@ -155,9 +163,26 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
   unsigned long long tlast = __builtin_readcyclecounter();
 #define K9S_TR(k, t0) do { if (lane == 0) atomicAdd(&X.tr[k], (uint32_t)(__builtin_readcyclecounter() - (t0))); } while (0)
 #define K9S_NOW() __builtin_readcyclecounter()
+  // wave 0's wait for a run, split (kb_k9.hpp: K9_WSPLIT_*).  ws_state: what the last look that had to go on found missing — 1: only the candidates,
+  // 2: only dirty keys, 3: both; ws_ts: since when.  A look is a poll of ~150 clocks (one LDS load, s_sleep 1): words that arrive between
+  // two looks count as "both"
+  uint32_t ws_prev_r = 0u;   // rows of the run in front
+#define K9S_WAIT_BEGIN() const unsigned long long ws_t0 = __builtin_readcyclecounter(); unsigned long long ws_ts = ws_t0; uint32_t ws_state = 0u
+#define K9S_WAIT_LOOK(p) do { const uint32_t st_ = (p) == 1u ? 1u : (((p) & 1u) ? 3u : 2u); if (st_ != ws_state) { ws_state = st_; ws_ts = __builtin_readcyclecounter(); } } while (0)
+#define K9S_WAIT_END() do { if (lane_i == 0u) {                                                                                              \
+    const unsigned long long now_ = __builtin_readcyclecounter();                                                                            \
+    uint32_t *w_ = &X.wsplit[(k == 0u ? 3u : (ws_prev_r == 1u ? 0u : (ws_prev_r <= 8u ? 1u : 2u))) * K9_WSPLIT_WORDS];                         \
+    w_[WS_RUNS] += 1u; w_[WS_CLK] += (uint32_t)(now_ - ws_t0);                                                                               \
+    if (ws_state == 1u) { w_[WS_CAND_RUNS] += 1u; w_[WS_CAND_CLK] += (uint32_t)(now_ - ws_t0); w_[WS_ONLY_CAND_CLK] += (uint32_t)(now_ - ws_ts); } \
+    else if (ws_state == 2u) { w_[WS_DK_RUNS] += 1u; w_[WS_DK_CLK] += (uint32_t)(now_ - ws_t0); w_[WS_ONLY_DK_CLK] += (uint32_t)(now_ - ws_ts); }  \
+    else if (ws_state == 3u) { w_[WS_BOTH_RUNS] += 1u; w_[WS_BOTH_CLK] += (uint32_t)(now_ - ws_t0); } } } while (0)
+#define K9S_WAIT_PREV(rows) do { ws_prev_r = (rows); } while (0)
 #else
 #define K9S_TR(k, t0) do { (void)(t0); } while (0)
 #define K9S_NOW() 0ull
+#define K9S_WAIT_BEGIN() do { } while (0)
+#define K9S_WAIT_END() do { } while (0)
+#define K9S_WAIT_PREV(rows) do { } while (0)
 #endif
   // how long a waiting prep / evaluating wave sleeps between two polls: s_sleep 1 (64 clocks).  Measured 0 .. 1 alike, longer slower
   // (profiles/round4/call18_19_20_polls_and_fence); the KB_SEL_SLEEP switch that swept it is gone
@@ -217,15 +242,23 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
       {   // the run's candidates (seq_cand) and its dirty keys (seq_dk[0..3]): five neighbouring words, one load per poll
         uint32_t spins = 0;
         bool ok = true;
+        K9S_WAIT_BEGIN();
         for (;;) {
           // lane_i 0: the candidates — settled ahead (seq_spec) when the run in front took all of its own, else settled behind it (seq_cand);
           // lanes 1..4: the dirty keys — the early ones (seq_early) when the run in front changed nothing else, else the final ones (seq_dk)
           const uint32_t *wp = (lane_i == 0u) ? (prev_all ? &Y.seq_spec : &Y.seq_cand) : (prev_chg ? &Y.seq_dk[(lane_i - 1u) & 3u] : &Y.seq_early[(lane_i - 1u) & 3u]);
           const uint32_t v = (lane_i < 5u) ? k9s_ld(wp) : 0xFFFFFFFFu;
+#ifdef KB_K9_TRACE
+          const uint32_t pend_ = (uint32_t)__ballot(v < k + 1u);   // bit 0: the candidates, bits 1..4: the dirty keys
+          if (pend_ == 0u) break;
+          K9S_WAIT_LOOK(pend_);
+#else
           if (__ballot(v < k + 1u) == 0ull) break;
+#endif
           if ((++spins & 31u) == 0u && (k9s_ld(&Y.err) || spins > K9S_SPIN_LIMIT)) { k9s_st(&Y.err, 1u); ok = false; break; }
           __builtin_amdgcn_s_sleep(1);
         }
+        K9S_WAIT_END();
         if (!ok) { reason_end = KB_REASON_INTERNAL; i_end = i0; break; }
       }
   //@@ w0_loads
@@ -659,6 +692,7 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
       }
       if (pc) { const uint32_t cp = rl32(cpos, pc - 1u); if (lane_i == 0) cursor[s] = cp + 1u; }
       prev_nd0 = nd; prev_pc = pc; prev_all = pc == ncand;
+      K9S_WAIT_PREV(r);
       K9_WAVE_FENCE();
       prev_chg = chg_any;   // (chg itself is for the evaluating waves: which slots)
       nd += pc; n_dirty_rows += n_dirty; n_runs += 1u; n_slow += plain0 ? 0u : 1u;
@@ -829,9 +863,20 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
         bool keep = lane < nf && !((bitmap[n >> 5] >> (n & 31)) & 1u);
         if (ahead) {   // m >= 1: run m - 1's candidates are final (seq_cand >= m); its nodes count as taken, its slots as used
           const K9Sel::Cand &CP = X.cand[(m - 1u) & 1u];
-          const uint32_t ncp = Y.ncand_at[(m - 1u) & 3u];
+          const uint32_t ncp = (uint32_t)__builtin_amdgcn_readfirstlane((int)Y.ncand_at[(m - 1u) & 3u]);   // <= K9_SEL_MAXRUN
           nd0 = Y.nd_at[(m - 1u) & 3u] + ncp;
-          for (uint32_t i = 0; i < ncp; i++) keep = keep && (nmaskbits - (CP.ckey[i] & nmaskbits)) != n;
+          // lane i holds candidate i's node (one LDS read, every lane written: readlane ignores EXEC); the membership test then runs on registers,
+          // a readlane, a compare and an OR per candidate, four candidates to a loop branch (the lanes beyond ncp hold no node: comparing against
+          // them changes nothing).  As a loop over CP.ckey[i] behind `keep &&` every step was an LDS round trip of its own and a branch, on the
+          // path between seq_cand = m and seq_spec = m + 1 that wave 0 waits for
+          uint32_t cn = KB_NONE_U32;
+          if (lane < ncp) cn = nmaskbits - (CP.ckey[lane] & nmaskbits);
+          bool taken = false;
+          for (uint32_t i = 0; i < ncp; i += 4u) {   // (i + 3 <= 31)
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; u++) taken |= rl32(cn, i + u) == n;
+          }
+          keep = keep && !taken;
         }
         const unsigned long long kb = __ballot(keep);
         const uint32_t rho = (uint32_t)__popcll(kb & lt);
@@ -880,6 +925,7 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
     tw[4] = (unsigned long long)X.tr[0] | ((unsigned long long)X.tr[1] << 32);
     tw[15] = (unsigned long long)X.tr[2] | ((unsigned long long)X.tr[3] << 32);
   }
+  if (tid < K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS && X.wsplit[tid]) atomicAdd(&k9s_wait_split[tid], (unsigned long long)X.wsplit[tid]);   // the result block has no word left
 #endif
   k9_epilogue(a, lo, k9_smem, tid, t_start, X.stat[0] | (X.stat[1] << 16), X.stat[2] | (X.stat[3] << 16), true, job_of_my_row);
 }
@@ -903,3 +949,21 @@ void kb_launch_commit_sel(const KbDev &d, const KbRound &r, void *stream) {
   if (solo && r.lists_ready == nullptr) grid = 1u;
   hipLaunchKernelGGL(k_commit_select, dim3(grid), dim3(K9_THREADS), sh, (hipStream_t)stream, ka);
 }
+
+#ifdef KB_K9_TRACE
+// the trace build's split of wave 0's wait (kb_k9.hpp: K9_WSPLIT_*) since the last call, beside the [kb K5 trace] lines (kb_engine_destroy, KB_K5_STATS=1)
+void kb_commit_sel_print_wait_split(FILE *f) {
+  unsigned long long h[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS] = {};
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(k9s_wait_split), sizeof(h)) != hipSuccess) return;
+  static const unsigned long long zero[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS] = {};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(k9s_wait_split), zero, sizeof(zero));
+  static const char *cls[K9_WSPLIT_CLASSES] = {"behind a run of 1 row", "behind a run of 2..8 rows", "behind a run of > 8 rows", "a round's first run"};
+  for (int c = 0; c < K9_WSPLIT_CLASSES; c++) {
+    const unsigned long long *w = h + c * K9_WSPLIT_WORDS;
+    fprintf(f, "[kb K5 trace] wave 0's poll, %-26s %8llu runs %12llu clocks | candidates last %8llu runs %12llu clocks (only they missing: %llu) | "
+               "dirty keys last %8llu runs %12llu clocks (only they missing: %llu) | both at the last look %8llu runs %12llu clocks | no wait %llu runs\n",
+            cls[c], w[WS_RUNS], w[WS_CLK], w[WS_CAND_RUNS], w[WS_CAND_CLK], w[WS_ONLY_CAND_CLK], w[WS_DK_RUNS], w[WS_DK_CLK], w[WS_ONLY_DK_CLK],
+            w[WS_BOTH_RUNS], w[WS_BOTH_CLK], w[WS_RUNS] - w[WS_CAND_RUNS] - w[WS_DK_RUNS] - w[WS_BOTH_RUNS]);
+  }
+}
+#endif

@@ -11,6 +11,10 @@
 
 thread_local std::string g_create_err;
 
+#ifdef KB_K9_TRACE
+void kb_commit_sel_print_wait_split(FILE *f);   // kb_commit_sel.hip, the trace build only
+#endif
+
 namespace kbe {
 
 // window buffers: one entry per task row of a round
@@ -224,6 +228,9 @@ void kb_engine_destroy(kb_engine *e) {
     for (int k = 0; k < 10; k++) fprintf(stderr, "[kb K5 trace] %-32s %14.0f clocks  (%.0f per run)\n", e->rounds_sel > e->rounds_run ? ph_sel[k] : ph[k], e->k5_trace[k], e->k5_trace[k] / runs);
     static const char *ph_role[4] = {"prep waves wait for their run's turn (sum of 3)", "prep waves wait for the walk's turn (sum of 3)", "wave 1 waits for the previous run", "wave 1 evaluates + publishes"};
     if (e->rounds_sel > e->rounds_run) for (int k = 10; k < 14; k++) fprintf(stderr, "[kb K5 trace] %-32s %14.0f clocks  (%.0f per run)\n", ph_role[k - 10], e->k5_trace[k], e->k5_trace[k] / runs);
+#ifdef KB_K9_TRACE
+    if (e->rounds_sel > e->rounds_run && hipSetDevice(e->device) == hipSuccess) kb_commit_sel_print_wait_split(stderr);
+#endif
   }
   (void)hipSetDevice(e->device);
   delete e;

@@ -51,6 +51,16 @@ struct K9Sync {
   uint32_t mdko[2][4];                // ... among the slots that were dirty before run k - 1 (the early evaluation; run k - 1's consumed candidates: dkb)
   uint32_t chg[2][10];                // [k & 1]: slots run k changed other than by consuming a clean candidate once (what an early evaluation for run k + 1 got wrong)
 };
+#ifdef KB_K9_TRACE
+// The trace build's split of wave 0's wait for a run (selection kernel).  Per class of run — the run in front had 1 row, 2..8 rows, more than
+// 8 rows, or there is none (a round's first run) — these words: runs, clocks in the poll; runs and clocks of the polls whose last missing word
+// was lane 0's (the candidates: seq_spec / seq_cand), was one of lanes 1..4's (the dirty keys: seq_early / seq_dk), was both at the last look;
+// and the clocks at the end of a poll during which ONLY the candidates / ONLY the dirty keys were missing.  (Runs whose first look found
+// everything: the rest.)  Summed over the rounds in device memory, printed by kb_commit_sel_print_wait_split
+#define K9_WSPLIT_CLASSES 4
+#define K9_WSPLIT_WORDS 10
+enum { WS_RUNS = 0, WS_CLK, WS_CAND_RUNS, WS_CAND_CLK, WS_DK_RUNS, WS_DK_CLK, WS_BOTH_RUNS, WS_BOTH_CLK, WS_ONLY_CAND_CLK, WS_ONLY_DK_CLK };
+#endif
 struct K9Sel {
   K9Sync sync;
   K9Prep prep[3];                     // one per prep wave
@@ -67,6 +77,10 @@ struct K9Sel {
   uint32_t pool[K9_MAXSLOTS + 64];
   uint32_t tr[4];                     // KB_K9_TRACE: cycles the other waves wait / work (kb_commit_sel.hip)
   uint32_t stat[4];                   // runs committed with every pick a clean first placement / by look-ahead passes / handed to the serial loop; look-ahead passes
+#ifdef KB_K9_TRACE
+  // wave 0's wait for a run, split by which word came last and by the rows of the run in front (kb_commit_sel.hip: K9S_WAIT_*; the trace build only)
+  uint32_t wsplit[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS];
+#endif
 };
 
 // dynamic LDS layout for a round of n_rows rows and n_shapes distinct shapes (sel: with the selection kernel's extra block)
