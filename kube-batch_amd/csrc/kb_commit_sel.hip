@@ -60,6 +60,7 @@ __device__ __forceinline__ bool k9s_wait(K9Sync &Y, const uint32_t *p, uint32_t 
 
 #ifdef KB_K9_TRACE
 __device__ unsigned long long k9s_wait_split[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS];   // kb_k9.hpp: K9_WSPLIT_*, summed over every round since the last print
+__device__ unsigned long long k9s_round_start[3];   // rounds; 10 ns units between the built run tables and the lists' tags; ... from there to the barrier behind the staged lists
 #endif
 
 __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs ka) {
@@ -92,31 +93,33 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
   K9Sel &X = *reinterpret_cast<K9Sel *>(k9_smem + lo.sel);
   K9Sync &Y = X.sync;
   const unsigned long long t_start = wall_clock64();
-  // (run lengths: from the run-start bitmap below — k9_prologue's own rule walks forward row by row)
+  // (run lengths: from the run-start bitmap below — k9_prologue_tables' own rule walks forward row by row)
+  // the job of "my" row (the epilogue marks it as allocated): the first part of the prologue issues the gather behind the descriptors, the value is
+  // wanted in the epilogue — and looked at nowhere in between (below: behind the lists), so that nobody waits for its round trip
+  uint32_t job_of_my_row = 0u;
 #ifdef KB_K9_TRACE
-  unsigned long long t_stage[2] = {0ull, 0ull};   // (trace build: the fixed parts of a round in units of the 100 MHz clock — staging, shape tables, run tables, loop)
-  const bool staged = k9_prologue(a, lo, k9_smem, tid, 0u, t_stage);
+  unsigned long long t_stage[4] = {0ull, 0ull, 0ull, 0ull};   // (trace build: the fixed parts of a round in units of the 100 MHz clock — staging, shape tables, run tables, the lists' tags, the lists, loop)
+  bool staged = k9_prologue_tables(a, lo, k9_smem, tid, 0u, &job_of_my_row, t_stage);
 #else
-  const bool staged = k9_prologue(a, lo, k9_smem, tid, 0u);
+  bool staged = k9_prologue_tables(a, lo, k9_smem, tid, 0u, &job_of_my_row);
 #endif
-  if (!staged) {   // a candidate list never came: nothing was evaluated or committed
+  if (!staged) {   // the arg-max launch's tags never came: nothing was evaluated or committed
     if (tid == 0) k9_publish_skipped(a);
     return;
   }
 
-  // the job of "my" row (the epilogue marks it as allocated): fetched now, wanted then
-  uint32_t job_of_my_row = 0u;
-  if (tid < W) job_of_my_row = a.dev->t_job[desc[tid].task];
   // ---- the runs of the window, by number: run k starts at row X.runs[k] (rinfo there holds its length, shape, flags, Resreq key mask).  A
-  //      row starts a run iff it cannot join its predecessor (k9_prologue's rule) or its stretch of joinable rows has reached a multiple of
+  //      row starts a run iff it cannot join its predecessor (k9_prologue_tables' rule) or its stretch of joinable rows has reached a multiple of
   //      the longest run.  W <= KB_K5_MAX_ROWS = 256: eight mask words.
+  //      All of it reads the descriptors only: in a launch that carries its repair workgroups it runs BESIDE the repair, in front of the wait
+  //      for the lists' tags, and behind the staged lists nothing is left but one barrier (k9_prologue_lists).
   if (tid < 8) { X.brk[tid] = 0u; X.stm[tid] = 0u; }
   if (tid < 4) { X.stat[tid] = 0u; X.tr[tid] = 0u; }
 #ifdef KB_K9_TRACE
   if (tid < K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS) X.wsplit[tid] = 0u;
 #endif
   if (tid < sizeof(K9Sync) / 4) reinterpret_cast<uint32_t *>(&Y)[tid] = 0u;   // every sequence word starts at 0; nd_at[0] = 0: run 0 finds no dirty slot
-  __syncthreads();
+  __syncthreads();   // (also: the prologue's rinfo is in LDS for the compaction below)
   if (tid < W) {
     bool brk = tid == 0;
     if (tid) {
@@ -149,17 +152,34 @@ __global__ void __launch_bounds__(K9_THREADS) k_commit_select(const K9KernArgs k
     uint32_t rlen = 0u;
     if (tid < K) { i0c = X.runs[tid]; rr = rinfo[i0c]; rlen = ((tid + 1u < K) ? (uint32_t)X.runs[tid + 1u] : W) - i0c; }   // the run ends where the next one starts
     __syncthreads();
-    if (tid < K) rinfo[tid] = make_uint4(i0c | (rlen << 16), rr.y, rr.z, rr.w);
-    __syncthreads();
+    if (tid < K) rinfo[tid] = make_uint4(i0c | (rlen << 16), rr.y, rr.z, rr.w);   // (in LDS for everybody behind the barrier that closes the prologue)
   }
+#ifdef KB_K9_TRACE
+  const unsigned long long t_built = wall_clock64();
+  staged = k9_prologue_lists(a, lo, k9_smem, tid, t_stage);
+#else
+  staged = k9_prologue_lists(a, lo, k9_smem, tid);
+#endif
+  if (!staged) {   // a candidate list never came: nothing was evaluated or committed
+    if (tid == 0) k9_publish_skipped(a);
+    return;
+  }
+  asm volatile("" : "+v"(job_of_my_row));   // the gather's value is first looked at HERE, behind the list loads' own wait (they were issued after it)
 
 #ifdef KB_K9_TRACE
   // make EXTRA=-DKB_K9_TRACE: wave 0's cycles — 0: waiting for a run's candidates and dirty keys, 3: rows (serial loop, tail, publish), 5: entries + first
   // rank, 6: deep passes, 7: picks + AddTask, 8: the all-clean path; X.tr: the prep waves' wait for their run's turn / for the walk's turn,
   // wave 1's wait for the previous run / its evaluation
   uint32_t tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // the fixed part of a round, in units of the 100 MHz clock: staging (tacc[1]), shape tables (tacc[9]), table building — rinfo, the run-start bitmap,
+  // X.runs, the compaction — (tacc[2]); the wait for the lists' tags and the list staging with its barrier go to k9s_round_start (no word left)
   const unsigned long long t_tab = wall_clock64();
-  tacc[1] = (uint32_t)(t_stage[0] - t_start); tacc[9] = (uint32_t)(t_stage[1] - t_stage[0]); tacc[2] = (uint32_t)(t_tab - t_stage[1]);
+  tacc[1] = (uint32_t)(t_stage[0] - t_start); tacc[9] = (uint32_t)(t_stage[1] - t_stage[0]); tacc[2] = (uint32_t)(t_built - t_stage[1]);
+  if (tid == 0) {
+    atomicAdd(&k9s_round_start[0], 1ull);
+    atomicAdd(&k9s_round_start[1], t_stage[2] - t_built);
+    atomicAdd(&k9s_round_start[2], t_stage[3] - t_stage[2]);
+  }
   unsigned long long tlast = __builtin_readcyclecounter();
 #define K9S_TR(k, t0) do { if (lane == 0) atomicAdd(&X.tr[k], (uint32_t)(__builtin_readcyclecounter() - (t0))); } while (0)
 #define K9S_NOW() __builtin_readcyclecounter()
@@ -957,6 +977,13 @@ void kb_commit_sel_print_wait_split(FILE *f) {
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(k9s_wait_split), sizeof(h)) != hipSuccess) return;
   static const unsigned long long zero[K9_WSPLIT_CLASSES * K9_WSPLIT_WORDS] = {};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(k9s_wait_split), zero, sizeof(zero));
+  unsigned long long rs[3] = {};
+  if (hipMemcpyFromSymbol(rs, HIP_SYMBOL(k9s_round_start), sizeof(rs)) == hipSuccess) {
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(k9s_round_start), zero, sizeof(rs));
+    const double n = (double)(rs[0] ? rs[0] : 1ull);
+    fprintf(f, "[kb K5 trace] round start, %llu rounds (10 ns units): wait for the lists' tags %llu (%.0f per round), list staging + barrier %llu (%.0f per round)\n",
+            rs[0], rs[1], (double)rs[1] / n, rs[2], (double)rs[2] / n);
+  }
   static const char *cls[K9_WSPLIT_CLASSES] = {"behind a run of 1 row", "behind a run of 2..8 rows", "behind a run of > 8 rows", "a round's first run"};
   for (int c = 0; c < K9_WSPLIT_CLASSES; c++) {
     const unsigned long long *w = h + c * K9_WSPLIT_WORDS;

@@ -222,7 +222,7 @@ void kb_engine_destroy(kb_engine *e) {
     static const char *ph[10] = {"barrier 1 (wave 0's wait)", "evaluate: candidates (wave 0)", "barrier 2", "rows", "prepare the next run",
                                 "rows, of runs with scalar dimensions", "runs with scalar dimensions (count)", "evaluate, of runs with scalar dimensions",
                                 "dirty-winner entries (count)", "loop top"};
-    static const char *ph_sel[10] = {"wave 0 waits for candidates + dirty keys", "staging: lists, descriptors (10 ns units, not clocks)", "run tables (10 ns units)", "rows: serial loop, tail, publish", "wave 0's loop (10 ns units)",
+    static const char *ph_sel[10] = {"wave 0 waits for candidates + dirty keys", "staging: descriptors, first lists (10 ns units, not clocks)", "table building: rinfo, run starts, compaction (10 ns units; the lists' tags and staging: the round start line)", "rows: serial loop, tail, publish", "wave 0's loop (10 ns units)",
                                     "selection: entries + first rank", "selection: deep passes", "selection: picks + AddTask", "selection: all picks clean", "shape tables (10 ns units)"};
     const double runs = (double)(e->k5_walks ? e->k5_walks : 1);
     for (int k = 0; k < 10; k++) fprintf(stderr, "[kb K5 trace] %-32s %14.0f clocks  (%.0f per run)\n", e->rounds_sel > e->rounds_run ? ph_sel[k] : ph[k], e->k5_trace[k], e->k5_trace[k] / runs);

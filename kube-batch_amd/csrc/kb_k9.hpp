@@ -336,13 +336,42 @@ __device__ __forceinline__ bool k9_wait_tags(const KbCommitArgs &a, K9Hdr &H, co
   return H.stop == 0u;
 }
 
+// Candidate lists (64-bit keys of K3 -> compact 32-bit keys), entries lbase0 .. tot - 1 of [S][L].  Every load of a thread is issued before the
+// first one is waited for: with one load per loop iteration, each waited for, a thread made 13 round trips to L2 / HBM one after the other at
+// 25 shapes x 257 entries — in front of every round, with nothing else on the CU to hide them.  agent: the lists were stored through by the
+// repair workgroups of this launch
+constexpr uint32_t K9_UL = 16;   // list entries per thread and batch
+__device__ __forceinline__ void k9_stage_lists(const KbCommitArgs &a, uint32_t *lists, const uint32_t tot, const uint32_t nb, const uint32_t nmaskbits, const bool agent,
+                                               const uint32_t tid, const uint32_t lbase0) {
+  for (uint32_t lbase = lbase0; lbase < tot; lbase += K9_THREADS * K9_UL) {
+    unsigned long long lv[K9_UL];
+#pragma unroll
+    for (uint32_t u = 0; u < K9_UL; u++) {   // (clamped, not predicated: S >= 1 with W >= 1)
+      const unsigned long long *kp = &a.keys[min(lbase + u * K9_THREADS + tid, tot - 1u)];
+      lv[u] = agent ? __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *kp;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < K9_UL; u++) {
+      const uint32_t idx = lbase + u * K9_THREADS + tid;
+      const unsigned long long k64 = lv[u];
+      if (idx < tot) lists[idx] = k64 ? (((KB_KEY_SCORE(k64) + 1u) << nb) | (nmaskbits - KB_KEY_NODE(k64))) : 0u;
+    }
+  }
+}
+
+// The prologue has two parts.  k9_prologue_tables: everything that reads no candidate list of a launch that carries its own repair workgroups
+// (KbRound::lists_ready) — nothing the second stream wrote is read before the arg-max launch's tags are seen (the row descriptors come from its
+// matrix launch), then descriptors, cursors, shape tables, sinit, rinfo.  k9_prologue_lists: the lists, behind the repair workgroups' tags, and
+// the barrier behind which the round is staged.  Without repair workgroups in the launch (first and re-planned rounds, KB_FUSE_REPAIR=0) the
+// lists ride in the first part's batch with the descriptors — one round trip — and the second part is the barrier alone.  What a kernel does
+// between the two runs beside the repair (the selection kernel: its run tables); rinfo is written by the first part WITHOUT a barrier behind it.
+// Either returns false when a tag never came: the caller publishes KB_REASON_SKIPPED and leaves.
 // maxrun: longest run of rows that share one evaluation (K9_MAXRUN); 0: the caller derives the run lengths itself (the selection kernel: from its
-// run-start bitmap).  `stamps` (trace builds): the 100 MHz clock behind the staging barrier and behind the shape tables.
-// A launch that carries its own repair workgroups (KbRound::lists_ready): nothing the second stream wrote is read before the arg-max launch's
-// tags are seen (the row descriptors come from its matrix launch), everything that does not need the lists is staged next, and the lists last,
-// behind the repair workgroups' tags.  Returns false when a tag never came: the caller publishes KB_REASON_SKIPPED and leaves.
-__device__ __forceinline__ bool k9_prologue(const KbCommitArgs &a, const K9Layout &lo, unsigned char *k9_base_, const uint32_t tid, const uint32_t maxrun,
-                                            unsigned long long *stamps = nullptr) {
+// run-start bitmap).  row_job (when asked for): t_job of row `tid`'s task, the gather issued as soon as the descriptors are in LDS — nobody has warmed
+// those lines, and the value is not wanted before the epilogue.  `stamps` (trace builds): the 100 MHz clock behind the staging barrier and
+// behind the shape tables; the second part: behind the lists' tags and behind the closing barrier.
+__device__ __forceinline__ bool k9_prologue_tables(const KbCommitArgs &a, const K9Layout &lo, unsigned char *k9_base_, const uint32_t tid, const uint32_t maxrun,
+                                                   uint32_t *row_job = nullptr, unsigned long long *stamps = nullptr) {
   const uint32_t S = a.n_mrows, W = a.n_rows;
   K9_LDS_VIEWS(lo)
   (void)slots; (void)rowres; (void)ldec; (void)dk; (void)ckey; (void)cpos; (void)RS;
@@ -353,27 +382,10 @@ __device__ __forceinline__ bool k9_prologue(const KbCommitArgs &a, const K9Layou
     __syncthreads();
     if (!k9_wait_tags<true>(a, H, a.round->ready, a.round->ready_tag, S, tid)) return false;
   }
-  // Candidate lists (64-bit keys of K3 -> compact 32-bit keys) and row descriptors.  Every load of a thread is issued before the first one is
-  // waited for: with one load per loop iteration, each waited for, a thread made 13 + 4 round trips to L2 / HBM one after the other at
-  // 25 shapes x 257 entries and 256 rows — in front of every round, with nothing else on the CU to hide them
-  constexpr uint32_t UD = 4, UL = 16;
+  // Row descriptors (and, not fused, the lists).  Every load of a thread is issued before the first one is waited for (k9_stage_lists): 13 + 4
+  // round trips one after the other at 25 shapes x 257 entries and 256 rows otherwise
+  constexpr uint32_t UD = 4, UL = K9_UL;
   const uint32_t tot = S * Lp;   // [S][L], Lp == L
-  auto stage_lists = [&](uint32_t lbase0) {
-    for (uint32_t lbase = lbase0; lbase < tot; lbase += K9_THREADS * UL) {
-      unsigned long long lv[UL];
-#pragma unroll
-      for (uint32_t u = 0; u < UL; u++) {   // (clamped, not predicated: S >= 1 with W >= 1)
-        const unsigned long long *kp = &a.keys[min(lbase + u * K9_THREADS + tid, tot - 1u)];
-        lv[u] = fused ? __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *kp;   // (fused: stored through by the repair workgroups of this launch)
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < UL; u++) {
-        const uint32_t idx = lbase + u * K9_THREADS + tid;
-        const unsigned long long k64 = lv[u];
-        if (idx < tot) lists[idx] = k64 ? (((KB_KEY_SCORE(k64) + 1u) << nb) | (nmaskbits - KB_KEY_NODE(k64))) : 0u;
-      }
-    }
-  };
   {
     const unsigned long long *dsrc = reinterpret_cast<const unsigned long long *>(a.desc);
     unsigned long long *ddst = reinterpret_cast<unsigned long long *>(desc);
@@ -395,11 +407,18 @@ __device__ __forceinline__ bool k9_prologue(const KbCommitArgs &a, const K9Layou
         const unsigned long long k64 = lv[u];
         if (idx < tot) lists[idx] = k64 ? (((KB_KEY_SCORE(k64) + 1u) << nb) | (nmaskbits - KB_KEY_NODE(k64))) : 0u;
       }
-      stage_lists(K9_THREADS * UL);
+      k9_stage_lists(a, lists, tot, nb, nmaskbits, false, tid, K9_THREADS * UL);
     }
   }
   for (uint32_t s = tid; s < S; s += K9_THREADS) cursor[s] = 0;
   __syncthreads();
+  if (row_job) {
+    // s_waitcnt vmcnt(0), on every path: the loads above are all consumed, but their waits sit inside the `idx < tot` branches, and what the compiler's
+    // counter bookkeeping carries out of those (registers it takes for still in flight) becomes a vmcnt(0) in front of the next write to each of them —
+    // which, once the gather is out, waits for the gather.  With the books clean here, nothing waits for it before somebody looks at its value
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (tid < W) *row_job = a.dev->t_job[desc[tid].task];
+  }
   if (stamps) stamps[0] = wall_clock64();
   // shape -> one of its rows (any: rows of a shape agree on everything the evaluation reads)
   for (uint32_t i = tid; i < W; i += K9_THREADS) shp[desc[i].slot] = i;
@@ -434,12 +453,23 @@ __device__ __forceinline__ bool k9_prologue(const KbCommitArgs &a, const K9Layou
       while (r < maxrun && i + r < W && desc[i + r].slot == sl && desc[i + r].flags == fl && desc[i + r].resmask == km) r++;
     rinfo[i] = make_uint4(r, sl, fl, km);
   }
-  if (fused) {   // the candidate lists last: everything above ran beside the workgroups that repair them
-    if (!k9_wait_tags<false>(a, H, a.round->lists_ready, a.round->lists_tag, S, tid)) return false;
-    stage_lists(0u);
-  }
-  __syncthreads();
   return true;
+}
+__device__ __forceinline__ bool k9_prologue_lists(const KbCommitArgs &a, const K9Layout &lo, unsigned char *k9_base_, const uint32_t tid, unsigned long long *stamps = nullptr) {
+  K9_LDS_VIEWS(lo)
+  (void)slots; (void)rowres; (void)sinit; (void)shapes; (void)desc; (void)rinfo; (void)ldec; (void)dk; (void)ckey; (void)cpos; (void)cursor; (void)shp; (void)bitmap; (void)RS;
+  if (a.round->lists_ready != nullptr) {   // the candidate lists last: everything before ran beside the workgroups that repair them
+    if (!k9_wait_tags<false>(a, H, a.round->lists_ready, a.round->lists_tag, a.n_mrows, tid)) return false;
+    if (stamps) stamps[2] = wall_clock64();
+    k9_stage_lists(a, lists, a.n_mrows * Lp, nb, nmaskbits, true, tid, 0u);
+  } else if (stamps) stamps[2] = wall_clock64();
+  __syncthreads();
+  if (stamps) stamps[3] = wall_clock64();
+  return true;
+}
+// both parts back to back (the run kernel: its run table is the first part's rinfo)
+__device__ __forceinline__ bool k9_prologue(const KbCommitArgs &a, const K9Layout &lo, unsigned char *k9_base_, const uint32_t tid, const uint32_t maxrun) {
+  return k9_prologue_tables(a, lo, k9_base_, tid, maxrun) && k9_prologue_lists(a, lo, k9_base_, tid);
 }
 
 // ---------------- epilogue (all threads): dirty slots, decision records, task table, result words, host mirror ----------------
