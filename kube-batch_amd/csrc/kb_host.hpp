@@ -8,7 +8,10 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -38,6 +41,31 @@ struct Policy {
   // Reclaimable (session_plugins.go:80-119): the same with EnabledReclaimable (conformance, gang, proportion own a rule)
   std::vector<std::vector<uint8_t>> reclaim_tiers;
   bool gang_job_pipelined = false;       // JobPipelined (session_plugins.go:202-222 + gang.go:126-129)
+};
+
+// every scorer yields 0..10 (NodeAffinity after its NormalizeReduce too): the largest weighted sum, which the matrix stores as u16.  The inter-pod
+// priority's weight counts in sessions that carry its tables
+inline long long max_score(const Policy &pol, bool with_podaffinity) {
+  return 10ll * ((long long)pol.wL + pol.wM + pol.wB + pol.wNA + (with_podaffinity ? pol.wPA : 0));
+}
+// 64-bit words per mask of `nbits` bits; a mask without bits still has a word (no table is indexed with a zero stride)
+inline uint32_t mask_words(uint64_t nbits) { return nbits ? (uint32_t)((nbits + 63) / 64) : 1u; }
+// the statuses api.AllocatedStatus names (api/helpers.go:64-71): what drf and proportion count as allocated (drf.go:71-77)
+inline bool is_allocated_status(int st) { return st == KB_TASK_BOUND || st == KB_TASK_BINDING || st == KB_TASK_RUNNING || st == KB_TASK_ALLOCATED; }
+
+// KB_LOAD_TRACE=1: where a load's time goes, phase by phase, on stderr (the Go action loads a session every cycle).  mark(what): the time since the
+// last mark, as "<prefix><what, padded to width> <ms> ms"
+struct PhaseTrace {
+  const char *prefix; int width; double t_mark;
+  PhaseTrace(const char *p, int w) : prefix(p), width(w), t_mark(now()) {}
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void mark(const char *what) {
+    static const bool on = [] { const char *v = getenv("KB_LOAD_TRACE"); return v && v[0] == '1'; }();
+    if (!on) return;
+    const double t = now();
+    fprintf(stderr, "%s%-*s %8.3f ms\n", prefix, width, what, t - t_mark);
+    t_mark = t;
+  }
 };
 
 // ---- host mirror of the session ----
@@ -120,6 +148,17 @@ struct HostSession {
   std::vector<double> queue_alloc;         // [Q][R]
   std::vector<double> queue_share;         // [Q]
   std::vector<int32_t> job_ready;          // [J] ReadyTaskNum
+  // a fresh session, but the T-sized arrays keep their storage from the last load (same cluster, next cycle: no allocation, no page faults)
+  void recycle() {
+    HostSession old = std::move(*this);
+    *this = HostSession();
+    t_res = std::move(old.t_res); t_init = std::move(old.t_init); t_res_rows = std::move(old.t_res_rows); t_resmask = std::move(old.t_resmask);
+    t_job = std::move(old.t_job); t_cls = std::move(old.t_cls); t_prio = std::move(old.t_prio); t_creation = std::move(old.t_creation);
+    t_status = std::move(old.t_status); t_node = std::move(old.t_node); t_nzc = std::move(old.t_nzc); t_nzm = std::move(old.t_nzm);
+    t_res_empty = std::move(old.t_res_empty); t_init_empty = std::move(old.t_init_empty);
+    t_feas_shape = std::move(old.t_feas_shape); t_row_shape = std::move(old.t_row_shape);
+    waterfill_on_device = old.waterfill_on_device;   // the engine's choice, made before the build
+  }
 };
 
 // ---- the plugin rules both host machines order by: the order machine (allocate / backfill, kb_order.cpp) and the evict machine

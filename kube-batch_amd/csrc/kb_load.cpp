@@ -127,8 +127,7 @@ static std::pair<uint32_t, uint32_t> plan_commit_window(uint32_t window, uint32_
 }
 // 32-bit keys: (score + 1) << node_bits | inverted node index
 static void check_key_range(const Policy &pol, uint32_t NP) {
-  const long long max_score = 10ll * ((long long)pol.wL + pol.wM + pol.wB + pol.wNA);
-  if (((unsigned long long)(max_score + 2) << kb_node_bits(NP)) > (1ull << 32))
+  if (((unsigned long long)(max_score(pol, false) + 2) << kb_node_bits(NP)) > (1ull << 32))
     throw EngineError(KB_E_UNSUPPORTED, "score range x node count exceeds the commit kernel's 32-bit keys");
 }
 static void upload_node_classes(LoadCtx &c) {
@@ -163,10 +162,7 @@ static void upload_task_arrays(LoadCtx &c) {
   d.t_status = up.copy_persistent(e->b_tstatus, hs.t_status.data(), T);
   d.t_node = up.copy_persistent(e->b_tnode, hs.t_node.data(), T);
   uint8_t *counted = up.stage<uint8_t>(e->b_tcounted, T);
-  for (uint32_t t = 0; t < T; t++) {
-    const int st = hs.t_status[t];
-    counted[t] = (st == KB_TASK_BOUND || st == KB_TASK_BINDING || st == KB_TASK_RUNNING || st == KB_TASK_ALLOCATED) ? 1 : 0;   // drf.go:71-77
-  }
+  for (uint32_t t = 0; t < T; t++) counted[t] = is_allocated_status(hs.t_status[t]) ? 1 : 0;   // drf.go:71-77
   d.t_counted = up.commit(counted);
   e->b_tbind.alloc(sizeof(uint32_t) * (T ? T : 1));
   e->b_jallocated.alloc(J ? J : 1);
@@ -200,7 +196,7 @@ static void upload_host_ports(LoadCtx &c) {
   kb_engine *e = c.e; const kb_snapshot *sn = c.sn; KbDev &d = e->dev; Uploader &up = c.up; HostSession &hs = e->hs;
   if (!(sn->node_ports || sn->task_port_want || sn->task_port_conflict)) return;
   const uint32_t N = d.N, NP = c.NP, T = d.T;
-  const size_t Wh = sn->port_words ? sn->port_words : 1;   // 64-bit words per mask; word 0 here, the others below
+  const size_t Wh = mask_words(64ull * sn->port_words);   // 64-bit words per mask; word 0 here, the others below
   std::vector<unsigned long long> np_(NP, 0ull), tw(T ? T : 1, 0ull), tc(T ? T : 1, 0ull);
   bool any = false;
   for (uint32_t n = 0; n < N && sn->node_ports; n++) { np_[n] = sn->node_ports[(size_t)n * Wh]; any = any || np_[n]; }
@@ -243,7 +239,7 @@ static void upload_affinity_table(LoadCtx &c) {
       if (cnt) { has[tc] = 1; any = true; }
     }
   if (!any || e->pol.wNA == 0) return;
-  if (e->pol.wNA < 0 || 10 * (e->pol.wL + e->pol.wM + e->pol.wB + e->pol.wNA) > 65535)
+  if (e->pol.wNA < 0 || max_score(e->pol, false) > 65535)
     throw EngineError(KB_E_UNSUPPORTED, "nodeorder weights exceed the 16-bit score range");
   hs.has_affinity = true;
   hs.cls_has_aff = has;
@@ -256,7 +252,7 @@ static void upload_interpod_tables(LoadCtx &c) {
   d.ip_Wc = d.ip_Wp = 1; d.wPA = e->pol.wPA;
   if (!ip) return;
   const uint32_t N = d.N, T = d.T, C = ip->n_counters, P = ip->n_classes, D = ip->n_domains;
-  const uint32_t Wc = C ? (C + 63) / 64 : 1, Wp = P ? (P + 63) / 64 : 1;
+  const uint32_t Wc = hs.ip_Wc, Wp = hs.ip_Wp;
   // [rows][N] -> [max(rows, 1)][NP], the pad (and the row of a table without rows) KB_NONE / 0
   d.ip_ctr_dom = up.padded<uint32_t>(e->b_ip_cdom, ip->ctr_dom, C, N, c.NP, KB_NONE);
   d.ip_cls_dom = up.padded<uint32_t>(e->b_ip_pdom, ip->cls_dom, P, N, c.NP, KB_NONE);
@@ -363,17 +359,9 @@ int kb_session_load(kb_engine *e, const kb_snapshot *sn) {
     const uint32_t NP = ((sn->n_nodes + KB_NODE_PAD - 1) / KB_NODE_PAD) * KB_NODE_PAD + (sn->n_nodes == 0 ? KB_NODE_PAD : 0);
     LoadCtx c{e, sn, Uploader(e->load_arena, e->stream), NP, {}, {}};
     hs.waterfill_on_device = e->device_waterfill && e->pol.has_proportion;
-    // KB_LOAD_TRACE=1: where a load's time goes, phase by phase, on stderr (the Go action loads a session every cycle)
-    static const bool load_trace = [] { const char *v = getenv("KB_LOAD_TRACE"); return v && v[0] == '1'; }();
-    double t_mark = now_ms();
-    auto mark = [&](const char *what) {
-      if (!load_trace) return;
-      const double t = now_ms();
-      fprintf(stderr, "kb_session_load: %-28s %8.3f ms\n", what, t - t_mark);
-      t_mark = t;
-    };
+    PhaseTrace trace("kb_session_load: ", 28);
     build_host_session(sn, e->pol, NP, hs, c.t_active, c.nmask);   // kb_session.cpp: validation, shapes, plugin OnSessionOpen state
-    mark("build_host_session");
+    trace.mark("build_host_session");
     e->evictions.clear();
     // ---- device upload: sources through the pinned area, copies asynchronous on the engine's stream, ONE synchronisation: reduce_and_finish's
     e->load_arena.reset();
@@ -386,21 +374,21 @@ int kb_session_load(kb_engine *e, const kb_snapshot *sn) {
     upload_node_state(c);
     std::tie(e->eff_window, e->shape_cap) = plan_commit_window(e->window, NP, hs.R);
     check_key_range(e->pol, NP);
-    mark("node arrays, window");
+    trace.mark("node arrays, window");
     upload_node_classes(c);
     upload_task_arrays(c);
-    mark("task arrays");
+    trace.mark("task arrays");
     upload_compat_table(c);
     upload_host_ports(c);
     upload_affinity_table(c);
     upload_interpod_tables(c);
-    mark("classes, ports, inter-pod");
+    trace.mark("classes, ports, inter-pod");
     upload_jobs_and_queues(c);
-    mark("jobs, queues, deserved");
+    trace.mark("jobs, queues, deserved");
     take_pristine_copies(e);
-    mark("pristine copies (queued)");
+    trace.mark("pristine copies (queued)");
     reduce_and_finish(e, wf_flight);
-    mark("aggregates (device reduction, the load's one synchronisation)");
+    trace.mark("aggregates (device reduction, the load's one synchronisation)");
   });
 }
 

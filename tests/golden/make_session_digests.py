@@ -31,6 +31,13 @@ def snapshots():
         yield f"raw{seed}", rawgen.raw_snapshot(seed)
     for seed in range(4):
         yield f"interpod{seed}", ipc.interpod_case(seed, False)[1]
+    # host-port masks of several words (pods that reach beyond word 0), and R = 16
+    import test_gpu_wideports as gw
+    nodes, queues, groups, pods = gw._objects()
+    wide = kbm.snapshot.flatten(nodes, pods, groups, queues)
+    assert wide.port_words >= 2 and wide.task_port_want[:, 1:].any()
+    yield "wideports_objects", wide
+    yield "config4_x0.02", kbm.snapshot.synth(kbm.snapshot.synth_config(4, 0.02))
 
 
 def digests():

@@ -219,7 +219,15 @@ uint64_t eh_digest(const EH *h) {
   for (const Res &r : s.deserved) { mix(r.v, sizeof(r.v)); mix(&r.mask, sizeof(uint32_t)); }
   const uint32_t n[4] = {s.n_feas_shapes, s.n_row_shapes, s.n_tc, s.n_nc};
   mix(n, sizeof(n));
-  if (s.port_xw) { vec(s.t_want_x); vec(s.t_conf_x); vec(s.t_wide); }   // host-port masks of several words (the pinned digests predate them: one-word sessions hash as before)
+  if (s.port_xw) { vec(s.t_want_x); vec(s.t_conf_x); vec(s.t_wide); }   // host-port masks of several words: one-word sessions hash without them
+  const uint8_t whole = s.whole ? 1 : 0;
+  mix(&whole, 1); vec(s.init_empty_tasks);
+  for (const Res &r : s.queue_request) { mix(r.v, sizeof(r.v)); mix(&r.mask, sizeof(uint32_t)); }
+  if (s.has_interpod) {   // the kb_interpod tables kept for the evict actions
+    const uint32_t g[5] = {s.ip_C, s.ip_D, s.ip_P, s.ip_Wc, s.ip_Wp};
+    mix(g, sizeof(g));
+    vec(s.ip_task_inc); vec(s.ip_task_forbid); vec(s.ip_task_cls_inc); vec(s.ip_task_require); vec(s.ip_task_self); vec(s.ip_ctr_dom);
+  }
   return x;
 }
 

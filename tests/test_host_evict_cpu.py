@@ -407,6 +407,89 @@ def test_malformed_snapshots_are_refused(harness):
         assert err.value.code == code, (mutate.__name__, str(err.value))
 
 
+def _refusal(harness, cfg, snap, patch_abi=None):
+    """(code, eh_error text) of the session build for `snap`; patch_abi(kb_snapshot) edits what to_abi() cannot express"""
+    h = C.c_void_p(harness.eh_create())
+    cfg_abi, keep = cfg.to_abi()
+    snap_abi = snap.to_abi()
+    if patch_abi:
+        patch_abi(snap_abi)
+    R, J, Q = snap.n_res, snap.n_jobs, snap.n_queues
+    z = [np.zeros((max(J, 1), R)), np.zeros(max(J, 1)), np.zeros((max(Q, 1), R)), np.zeros(max(Q, 1))]
+    rc = harness.eh_load(h, C.byref(cfg_abi), C.byref(snap_abi), *[_vp(a) for a in z])
+    text = harness.eh_error(h).decode()
+    harness.eh_destroy(h)
+    return rc, text
+
+
+def _refusal_order_cases():
+    """name -> (cfg, snapshot with TWO defects, patch_abi or None, the refusal build_host_session answers: code and text)"""
+    import test_interpod_oracle_cpu as ipc
+    full = conf.load_scheduler_conf(cases.CONF_FULL.format(actions="allocate, backfill"))
+    assert _has(full, "proportion")
+    base = cases._evict_case(3)[1]
+    T = int(base.n_tasks)
+
+    def interpod_base():
+        s = copy_snapshot(ipc.interpod_case(0)[1])
+        assert s.interpod is not None
+        s.interpod = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s.interpod.items()}
+        return s
+    out = {}
+
+    s = copy_snapshot(base)
+    s.node_alloc_mem[-1] = -1; s.job_task_begin[0] = 1
+    out["negative node quantity / job_task_begin gap"] = (full, s, None, (abi.KB_E_INVALID, "negative node quantity"))
+
+    s = copy_snapshot(base)
+    s.task_node[T - 1] = s.n_nodes; s.task_job[0] = s.n_jobs - 1
+    out["task_node out of range / task in the wrong job"] = (full, s, None, (abi.KB_E_INVALID, "task_node out of range"))
+
+    s = rawgen.widen_ports(interpod_base(), 9700, words=2)
+    s.task_port_want[3, 1] |= np.uint64(1) << np.uint64(5); s.task_port_conflict[3, 1] &= ~(np.uint64(1) << np.uint64(5))
+
+    def drop_sig_weight(k):
+        k.interpod.contents.sig_weight = C.POINTER(C.c_int32)()
+    out["wide-port want outside conflict in word 1 / missing inter-pod table"] = (
+        full, s, drop_sig_weight, (abi.KB_E_INVALID, "a pod's host ports must conflict with themselves (want is not a subset of conflict)"))
+
+    s = interpod_base()
+    s.interpod["n_domains"] = 0; s.task_init_resreq[0, 0] = s.task_resreq[0, 0] - 1.0
+    out["inter-pod n_domains = 0 / InitResreq < Resreq"] = (full, s, None, (abi.KB_E_INVALID, "inter-pod: n_domains outside 1..N"))
+
+    s = copy_snapshot(base)
+    s.task_status[T - 1] = 200; s.task_resreq[0, 0] = -1.0
+    out["bad task status / negative request on a lower task"] = (full, s, None, (abi.KB_E_INVALID, "bad task status"))
+
+    s = copy_snapshot(base)
+    s.task_init_resreq[1, T // 2] = s.task_resreq[1, T // 2] - 1.0; s.job_queue[0] = abi.KB_NONE
+    out["InitResreq < Resreq / job on a missing queue, proportion"] = (full, s, None, (abi.KB_E_UNSUPPORTED, "InitResreq < Resreq"))
+
+    heavy = conf.load_scheduler_conf(cases.CONF_FULL.format(actions="allocate, backfill"))
+    for tier in heavy.tiers:
+        for po in tier:
+            if po.name == "nodeorder":
+                po.arguments = {"podaffinity.weight": "7000"}      # 10 * (1 + 0 + 1 + 1 + 7000) > 65535; without it the sum is 30
+    s = interpod_base()
+    s.interpod["task_sig"][s.n_tasks - 1] = int(s.interpod["n_sigs"])
+    out["16-bit bound with podaffinity.weight / task_sig out of range"] = (heavy, s, None, (abi.KB_E_INVALID, "inter-pod: task_sig out of range"))
+    out["16-bit bound with podaffinity.weight alone (the pair above does plant it)"] = (
+        heavy, interpod_base(), None, (abi.KB_E_UNSUPPORTED, "nodeorder weights (with podaffinity.weight) exceed the 16-bit score range"))
+    return out
+
+
+def test_session_build_refusal_order(harness, monkeypatch):
+    """Which refusal a snapshot with TWO defects gets is part of the ABI contract (tests/test_emu_engine_cpu.py: test_load_refusal_order
+    pins it for the device half of the load): build_host_session answers in the order of its steps, and the task pass reports a bad
+    status behind the whole pass, in front of any part's refusal.  Code and text as the session build gave them before it was cut into
+    steps; one host thread and the split passes."""
+    todo = _refusal_order_cases()
+    for split_words in ("1", str(1 << 40)):
+        monkeypatch.setenv("KB_HOST_SPLIT_WORDS", split_words)
+        for name, (cfg, snap, patch, want) in todo.items():
+            assert _refusal(harness, cfg, snap, patch) == want, (name, split_words)
+
+
 def test_job_with_a_missing_queue(harness, oracle_mod):
     """job_queue >= n_queues is "queue not found" (allocate.go:56-60).  With proportion loaded the reference panics in OnSessionOpen
     (proportion.go:70-73: ssn.Queues[job.Queue].UID on a nil queue): the oracle reports the panic, kb_session_load answers
